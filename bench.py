@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark: clips/sec, encode + generate, eilev-blip2-opt-2.7b, 8 frames x 16 in-context (BASELINE.json).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One STEP = one pass of the hot path over one batch of synthetic input per GPU: `--samples` (default 32)
@@ -11,8 +11,11 @@ Q-Former -> projection -> [all-gather of clip tokens when N > 1] -> embed+scatte
 `--samples` samples; clips of the global step are dealt round-robin over the ranks (eilev_amd/sharding.py).
 
 Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel = the ViT MLP GEMM,
-timed live with hipEvents on the launch stream inside the timed region) and `cpu_baseline` (the CPU oracle
-timed on a bounded sample of the same workload, rank 0 at N = 1 only).
+timed live with hipEvents on the launch stream inside the timed region).  A plain run sets up, warms up, times
+the steps, writes its outputs (`--dump-outputs`) and prints that line.  `--full` adds everything that takes work
+of its own after the timed steps: the oracle check and the reference-fixture replay (`verified`), `cpu_baseline`
+(the CPU oracle and stock transformers timed on a bounded sample of the same workload, rank 0 at N = 1 only),
+the strong-scaling phase, the rocprofv3 --pmc re-measurement of `roofline.traffic` and, at N > 1, `sharded_check`.
 """
 from __future__ import annotations
 
@@ -491,12 +494,35 @@ def measure_traffic_pmc(shape: str = "fc1_ln", rows: int = 257 * 1088, kernel: s
     return {"fetch_kb": out["FETCH_SIZE"], "write_kb": out["WRITE_SIZE"], "launches": out["launches"], "dur_us": out["dur_us"]}, None
 
 
+def dump_outputs(outdir, ids, feats, rank, world, budget=32 << 20):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy — the generated ids (float64, exact) and a fixed, seeded sample
+    of rows of the projected clip tokens (float32; the whole tensor is ~180 MB at the default size).  The same arguments give the same
+    inputs and the same rows, so two builds compare output for output.  N > 1: every rank writes its own set (`_rank<r>`) within one budget."""
+    os.makedirs(outdir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    rows = feats.reshape(-1, feats.shape[-1])
+    n = min(rows.shape[0], max(1, budget // world // (4 * rows.shape[1])))
+    pick = np.sort(np.random.default_rng(0).choice(rows.shape[0], n, replace=False))
+    arrays = {"generated_ids": ids.cpu().numpy().astype(np.float64),
+              "clip_tokens_sample": rows[torch.from_numpy(pick).to(rows.device)].float().cpu().numpy(),
+              "clip_tokens_sample_rows": pick.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{sfx}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--samples", type=int, default=32, help="16-shot samples per GPU per step (<= 32: one decode batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64): the "
+                         "generated ids and a fixed, seeded row sample of the projected clip tokens (N > 1: one set per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes work of its own after the timed steps: oracle verification + reference-fixture replay, "
+                         "cpu_baseline, the strong-scaling phase, the live --pmc traffic measurement and (N > 1) sharded_check; the "
+                         "--no-* options below switch single legs of it off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline from ONE complete 16-shot sample on the host cores (17 clips encoded + L = 960 prefill + 32 tokens: "
                     "~1.5-2 minutes of CPU) instead of the default bounded sample that is extrapolated")
@@ -568,8 +594,8 @@ def main():
     seq_len = 1 + (N_CTX + 1) * 33 + N_CTX * 24 + 14
     weights = random_weights(cfg, dev)
     eng = HipEngine(cfg, weights, device=dev, lm_weights=args.lm_weights)
-    do_verify = world == 1 and not args.no_verify and args.lm == "opt27" and args.lm_weights == "bf16"
-    do_cpu = world == 1 and not args.no_cpu_baseline and args.lm == "opt27" and args.shots == 16
+    do_verify = args.full and world == 1 and not args.no_verify and args.lm == "opt27" and args.lm_weights == "bf16"
+    do_cpu = args.full and world == 1 and not args.no_cpu_baseline and args.lm == "opt27" and args.shots == 16
     if not (do_verify or do_cpu):
         del weights
     S = args.samples
@@ -644,6 +670,8 @@ def main():
         out = step()
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:  # before anything else runs on the engine
+        dump_outputs(args.dump_outputs, out, last["feats"], rank, world)
     # phase breakdown from events recorded on the launch stream inside the timed region (SURVEY §8d asks for these)
     phases = {"encode": 0.0, "prefill": 0.0, "decode": 0.0}
     marks = eng.timing
@@ -678,7 +706,7 @@ def main():
         dist.all_reduce(allp)
         per_rank_ms = [{"rank": r, "encode": round(float(allp[r, 0]), 2), "exchange_exposed": round(float(allp[r, 3]), 3),
                         "prefill": round(float(allp[r, 1]), 2), "decode": round(float(allp[r, 2]), 2)} for r in range(world)]
-        if not is_t5 and not args.no_verify:
+        if not is_t5 and args.full and not args.no_verify:
             # outside the timed region: every rank re-encodes the clips of ITS samples itself (the pixels of a peer are its seed
             # away) and the rows that came through the exchange must be those rows, the ids of its samples the same ids
             first, cps = rank * S * (N_CTX + 1), N_CTX + 1
@@ -764,7 +792,7 @@ def main():
                                     "wait for the side stream before the language model"}
     exch.timing = None
     strong = None
-    if not args.no_strong and args.shots == 16:
+    if args.full and not args.no_strong and args.shots == 16:
         strong = strong_scaling_phase(eng, cfg, world, rank, dev, exch, is_t5, args.strong_samples)
 
     if rank == 0:
@@ -805,7 +833,7 @@ def main():
                     traffic = int((2 * tr["fetch_kb"] + tr["write_kb"]) * 1024)
             except OSError:
                 pass
-            live, why = (None, "--no-pmc") if args.no_pmc else (None, "N > 1") if world > 1 else \
+            live, why = (None, "re-measured with --full only") if not args.full else (None, "--no-pmc") if args.no_pmc else (None, "N > 1") if world > 1 else \
                 (None, "not the fc1 roofline kernel / launch shape") if "fc1" not in nm or S * (N_CTX + 1) % 136 else measure_traffic_pmc()
             src = "profiles/r05_gemm_traffic.json (rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE of this kernel at this launch shape; not re-measured in this run: " + str(why) + ")"
             if live:

@@ -57,10 +57,20 @@ def test_without_a_users_eilev_the_missing_module_is_a_clean_import_error(tmp_pa
     assert r.returncode == 0 and "ok2" in r.stdout, r.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/eilev"), reason="the reference checkout only exists in the build container")
-def test_against_the_reference_checkout_module_resolution():
-    """With the real reference behind this repo on sys.path every `eilev.*` module train_v2.py / the sample import is FOUND (their
-    third-party imports — pytorchvideo — are not installed here, so only resolution is checked, not execution)."""
+# the module files of the reference checkout's `eilev` package (names only; its __init__ files are empty)
+REFERENCE_LAYOUT = ["eilev/__init__.py", "eilev/data/__init__.py", "eilev/data/ego4d.py", "eilev/data/epic_kitchens.py", "eilev/data/frame.py",
+                    "eilev/data/utils.py", "eilev/model/__init__.py", "eilev/model/utils.py", "eilev/model/v1.py", "eilev/model/v2.py"]
+
+
+def test_against_the_reference_checkout_module_resolution(tmp_path):
+    """With a checkout laid out like the reference's behind this repo on sys.path every `eilev.*` module train_v2.py / the sample import is
+    FOUND, the un-ported ones in that checkout and the ported ones here (a stand-in with empty modules: only resolution is checked, not
+    execution)."""
+    for rel in REFERENCE_LAYOUT:
+        f = tmp_path / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text("")
+    ref = str(tmp_path)
     r = _run("""
         import importlib.util as u
         import eilev, eilev.data, eilev.model
@@ -68,8 +78,9 @@ def test_against_the_reference_checkout_module_resolution():
             spec = u.find_spec(name)
             assert spec is not None, name
             print(name, spec.origin)
-    """, "/root/reference")
+    """, ref)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = dict(l.split() for l in r.stdout.strip().splitlines())
-    assert lines["eilev.data.frame"].startswith("/root/reference/") and lines["eilev.model.v1"].startswith("/root/reference/")
+    assert lines["eilev.data.frame"].startswith(ref + os.sep) and lines["eilev.model.v1"].startswith(ref + os.sep)
+    assert lines["eilev.data.ego4d"].startswith(ref + os.sep)
     assert lines["eilev.model.v2"].startswith(ROOT) and lines["eilev.data.utils"].startswith(ROOT) and lines["eilev.model.utils"].startswith(ROOT)

@@ -139,7 +139,7 @@ def test_bench_launches_n_ranks_and_the_exchanged_rows_are_the_local_rows(world,
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--share-gpu", "--steps", "1", "--warmup", "0",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(world), "--share-gpu", "--steps", "1", "--warmup", "0",
                         "--samples", str(samples)], capture_output=True, text=True, timeout=900 if world < 8 else 1800, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

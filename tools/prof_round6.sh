@@ -20,7 +20,7 @@ python $R/tools/blas_yardstick.py > $O/r06_blas_yardstick.log 2>&1
 tail -8 $O/r06_blas_yardstick.log
 # 4) the default bench command (live traffic measurement, CPU baseline, verification) and the other configs
 cd $R
-timeout 1800 python bench.py --cpu-full 2> $O/r06_final_bench.err | tail -1 > $O/r06_final_bench.json
+timeout 1800 python bench.py --full --cpu-full 2> $O/r06_final_bench.err | tail -1 > $O/r06_final_bench.json
 timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-strong --no-pmc --lm t5xl 2>/dev/null | tail -1 > $O/r06_t5xl_bench_final.json
 timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-strong --no-pmc --lm opt67 --shots 32 --lm-weights fp8_mfma 2>/dev/null | tail -1 > $O/r06_opt67fp8_bench_final.json
 timeout 600 python bench.py --samples 1 --steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-strong --no-pmc 2>/dev/null | tail -1 > $O/r06_bench_latency.json
