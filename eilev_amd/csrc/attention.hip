@@ -411,8 +411,8 @@ __global__ __launch_bounds__(64 * NWQ) void attn_prefill_v2_kernel(const AttnArg
 
     for (int t = 0; t < ntiles; ++t) {
         const int cur = t & 1;
-        if (t + 1 < ntiles && !(a.dbg & 2)) stage_in(cur ^ 1, t + 1);
-        if (active && !(a.dbg & 1)) {
+        if (t + 1 < ntiles && !(a.dbg & DBG_ATTN_NO_PREFETCH)) stage_in(cur ^ 1, t + 1);
+        if (active && !(a.dbg & DBG_ATTN_NO_COMPUTE)) {
             const int kv0 = t * 64;
             int vis_end = kv_end;  // first key no row of this wave may see
             if (a.causal) vis_end = min(vis_end, min(a.sq - 1, q0 + 31) + off + 1);
@@ -692,7 +692,7 @@ __global__ __launch_bounds__(576) void attn_frame_kernel(const AttnArgs a) {
     load_q(pair, 0, qf[0]);
     if (two_tiles) load_q(pair, 1, qf[1]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const bool ts_on = (a.dbg & 256) && blockIdx.x == 0 && lane == 0;
+    const bool ts_on = (a.dbg & DBG_ATTN_FRAME_STAMPS) && blockIdx.x == 0 && lane == 0;
 #define FA_TS(ev)                                                                                  \
     do {                                                                                           \
         if (ts_on && it < 8) g_attn_ts[(wid * 8 + it) * 16 + (ev)] = __builtin_amdgcn_s_memtime(); \
@@ -791,21 +791,9 @@ int launch_attn_frame(const AttnArgs &a, hipStream_t s) {
     constexpr int CH = HD / 8;
     constexpr int NPIECE = (NT * 16 * CH + (12 - CH) + 63) / 64;
     constexpr int smem = 3 * NPIECE * 1024;
-    static bool attr_set = false;
-    static int num_cu = 0;
-    if (!attr_set) {
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attn_frame_kernel<HD, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int dev = 0;
-        EILEV_HIP_CHECK(hipGetDevice(&dev));
-        EILEV_HIP_CHECK(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        attr_set = true;
-    }
     const int npairs = a.batch * a.heads;
-    const int ncu = eilev_grid_cus() < num_cu ? eilev_grid_cus() : num_cu;
-    const int grid = npairs < ncu ? npairs : ncu;
-    hipLaunchKernelGGL((attn_frame_kernel<HD, NT>), dim3(grid), dim3(576), smem, s, a);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    const int grid = npairs < eilev_grid_cus() ? npairs : eilev_grid_cus();
+    return eilev_launch<attn_frame_kernel<HD, NT>>(dim3(grid), dim3(576), smem, s, a);
 }
 
 #include "attn_frame3.h"
@@ -814,16 +802,7 @@ template <int NWQ, int DB = 3, bool REL = false>
 int launch_attn_v2(const AttnArgs &a, hipStream_t s) {
     size_t smem = attn_v2_rel_offset(NWQ, a.hd) + (REL ? (size_t)(a.rel_n + 2 * ATTN_V2_REL_SLACK) * sizeof(float) : 0);
     const dim3 grid((a.sq + 32 * NWQ - 1) / (32 * NWQ), a.heads, a.batch), block(64 * NWQ);
-    if (smem > 64 * 1024) {
-        static bool attr = false;
-        if (!attr) {
-            EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attn_prefill_v2_kernel<NWQ, DB, REL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr = true;
-        }
-    }
-    hipLaunchKernelGGL((attn_prefill_v2_kernel<NWQ, DB, REL>), grid, block, smem, s, a);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    return eilev_launch<attn_prefill_v2_kernel<NWQ, DB, REL>>(grid, block, smem, s, a);
 }
 
 }  // namespace
@@ -843,20 +822,20 @@ int launch_attention(const AttnArgs &a_in, hipStream_t s) {
         return launch_attn_frame3<88, 17, true>(a, s);
     }
     // whole-frame ViT attention: S = 257 (17 tiles of 16), hd = 88, no mask, q / k / v rows of one fused buffer
-    if (!g_attn_force_v1 && !(a.dbg & 4) && !a.rel_tab && !a.drop_thr && a.hd == 88 && a.sq == a.skv && a.sq > 256 && a.sq <= 272 && !a.causal && !a.key_mask &&
+    if (!g_attn_force_v1 && !(a.dbg & DBG_ATTN_NO_FRAME) && !a.rel_tab && !a.drop_thr && a.hd == 88 && a.sq == a.skv && a.sq > 256 && a.sq <= 272 && !a.causal && !a.key_mask &&
         a.ldk == a.ldv && !(a.ldq & 3) && (int64_t)a.sq * a.ldk * 2 < 0x7fff0000ll) {
         // >= 512 frames: two wave groups one phase apart (attn_frame3.h; 512: with phase stamps): 2-13 % faster at 544 / 1088 frames over
         // six boxes (profiles/r03_attn_frame3.log), slower below ~384 frames (its slots are longer: more exposed at the start and the end
         // of a workgroup's walk).  Probe flag 16 forces it, 32 forbids it.
 #ifdef EILEV_PROBES
-        if (a.dbg & 1024) {  // TIMING PROBE (wrong results): q / k / v read as if stored head-major ([frame][head][token][88]: an image is 45 KB contiguous)
+        if (a.dbg & DBG_ATTN_HEAD_MAJOR) {  // TIMING PROBE (wrong results): q / k / v read as if stored head-major ([frame][head][token][88]: an image is 45 KB contiguous)
             a.ldq = a.ldk = a.ldv = a.hd;
             a.q_hs = a.k_hs = a.v_hs = (int64_t)a.sq * a.hd;
             a.k = a.q + (int64_t)a.sq * a.heads * a.hd;  // three planes per frame inside the fused q|k|v rows: the same bytes are read, none twice
             a.v = a.q + 2 * (int64_t)a.sq * a.heads * a.hd;
         }
 #endif
-        if (a.sq == 257 && !(a.dbg & 32) && ((a.dbg & (16 | 512)) || a.batch >= 512)) return launch_attn_frame3<88, 17>(a, s);
+        if (a.sq == 257 && !(a.dbg & DBG_ATTN_NO_FRAME3) && ((a.dbg & (DBG_ATTN_FRAME3 | DBG_ATTN_FRAME3_STAMPS)) || a.batch >= 512)) return launch_attn_frame3<88, 17>(a, s);
         return launch_attn_frame<88, 17>(a, s);
     }
     // hd = 64 with >= 128 query rows (the flan-t5 encoder: L = 960, relative position bias; also its bias-free long forms): round 5
@@ -871,7 +850,7 @@ int launch_attention(const AttnArgs &a_in, hipStream_t s) {
     if (!g_attn_force_v1 && !a.rel_tab && !a.drop_thr && a.hd == 128 && a.sq >= 64 && a.skv >= 64) {
         const int qt = (a.sq + 31) / 32;
 #ifdef EILEV_PROBES
-        if (a.dbg & 64) return launch_attn_v2<4, 4>(a, s);  // probe: 4 waves per workgroup (512 registers per wave, two blocks in flight)
+        if (a.dbg & DBG_ATTN_V2_4WAVES) return launch_attn_v2<4, 4>(a, s);  // probe: 4 waves per workgroup (512 registers per wave, two blocks in flight)
 #endif
         return qt >= 5 ? launch_attn_v2<8, 4>(a, s) : launch_attn_v2<4, 4>(a, s);
     }

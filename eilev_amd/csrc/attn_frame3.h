@@ -299,7 +299,7 @@ __global__ __launch_bounds__(512) void attn_frame3_kernel(const AttnArgs a) {
             const bf16x8 v8 = {lo.v[0], lo.v[1], lo.v[2], lo.v[3], hi.v[0], hi.v[1], hi.v[2], hi.v[3]};
             // rows past S and d past HD are dropped by the offset (out of the descriptor's range)
 #ifdef EILEV_PROBES
-            if (a.dbg & 2048) continue;  // TIMING PROBE (no output): the kernel without its O stores
+            if (a.dbg & DBG_ATTN_FRAME3_NO_STORES) continue;  // TIMING PROBE (no output): the kernel without its O stores
 #endif
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_o, v8), ro, (row < S && d0 + 8 <= HD) ? ob_off + 64 * m : 0x7ffffff0u, 0, 0);
         }
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(512) void attn_frame3_kernel(const AttnArgs a) {
     load_q01(pair);
     load_qc(pair);
     FA_VMCNT(0);
-    const bool ts_on = (a.dbg & 512) && blockIdx.x == 0 && lane == 0;
+    const bool ts_on = (a.dbg & DBG_ATTN_FRAME3_STAMPS) && blockIdx.x == 0 && lane == 0;
 #define FA_TS(ev)                                                                                  \
     do {                                                                                           \
         if (ts_on && it < 8) g_attn_ts[(wid * 8 + it) * 16 + (ev)] = __builtin_amdgcn_s_memtime(); \
@@ -665,19 +665,7 @@ int launch_attn_frame3(const AttnArgs &a, hipStream_t s) {
     constexpr int CH = HD / 8;
     constexpr int NPIECE = (NT * 16 * CH + (12 - CH) + 63) / 64;
     constexpr int smem = 3 * NPIECE * 1024 + 8 * 512;
-    static bool attr_set = false;
-    static int num_cu = 0;
-    if (!attr_set) {
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attn_frame3_kernel<HD, NT, HM>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int dev = 0;
-        EILEV_HIP_CHECK(hipGetDevice(&dev));
-        EILEV_HIP_CHECK(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        attr_set = true;
-    }
     const int npairs = a.batch * a.heads;
-    const int ncu = eilev_grid_cus() < num_cu ? eilev_grid_cus() : num_cu;
-    const int grid = npairs < ncu ? npairs : ncu;
-    hipLaunchKernelGGL((attn_frame3_kernel<HD, NT, HM>), dim3(grid), dim3(512), smem, s, a);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    const int grid = npairs < eilev_grid_cus() ? npairs : eilev_grid_cus();
+    return eilev_launch<attn_frame3_kernel<HD, NT, HM>>(dim3(grid), dim3(512), smem, s, a);
 }

@@ -430,17 +430,9 @@ int launch_attn_bwd_e(const AttnBwdArgs &a, hipStream_t s) {
     constexpr int DP = DB * 32, LDR = DP + 8;
     const size_t smem_q = (size_t)(2 * 64 * LDR + 64 * LDT) * 2 + (64 + 64 + 256) * 4 + 64 * 4;
     const size_t smem_kv = (size_t)(2 * 64 * LDR + 2 * 64 * LDT) * 2 + (64 + 64) * 4 + 64 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq_kernel<DB, EXTRA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q));
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_kernel<DB, EXTRA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DB, EXTRA>), dim3((a.sq + 63) / 64, a.heads, a.batch), dim3(256), smem_q, s, a);
-    EILEV_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DB, EXTRA>), dim3((a.skv + 63) / 64, a.heads, a.batch), dim3(256), smem_kv, s, a);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    const int rc = eilev_launch<attn_bwd_dq_kernel<DB, EXTRA>>(dim3((a.sq + 63) / 64, a.heads, a.batch), dim3(256), smem_q, s, a);
+    if (rc != EILEV_OK) return rc;
+    return eilev_launch<attn_bwd_dkv_kernel<DB, EXTRA>>(dim3((a.skv + 63) / 64, a.heads, a.batch), dim3(256), smem_kv, s, a);
 }
 template <int DB>
 int launch_attn_bwd(const AttnBwdArgs &a, hipStream_t s) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/eilev.h"
 
 typedef __bf16 bf16;
@@ -35,15 +37,42 @@ static inline int eilev_num_cu() {
 }
 
 // CUs the persistent kernels (one workgroup per CU: GEMM, frame attention) size their grids for: all of them, or fewer when the caller runs
-// them on a CU-masked stream next to another stream (probe switch eilev_debug_grid_cus; tools/overlap_probe.py).
+// them on a CU-masked stream next to another stream (probe switch eilev_debug_grid_cus; tools/overlap_probe.py).  Never more than the device has.
 extern int g_eilev_grid_cus;
-static inline int eilev_grid_cus() { return g_eilev_grid_cus > 0 ? g_eilev_grid_cus : eilev_num_cu(); }
+static inline int eilev_grid_cus() {
+    const int n = eilev_num_cu();
+    return g_eilev_grid_cus > 0 && g_eilev_grid_cus < n ? g_eilev_grid_cus : n;
+}
 
 #define EILEV_LAUNCH_CHECK()                           \
     do {                                               \
         hipError_t _e = hipGetLastError();             \
         if (_e != hipSuccess) return (int)_e;          \
     } while (0)
+
+// Launches the kernel instance KERNEL with `smem` bytes of dynamic LDS and checks the launch.  Before the instance is first launched with
+// more dynamic LDS than it was allowed so far, its hipFuncAttributeMaxDynamicSharedMemorySize is raised to the size asked for (once per
+// instance where the size is fixed).  hipFuncSetAttribute enqueues no stream work: this may run inside a graph capture.
+template <auto KERNEL, typename... Args>
+static inline int eilev_launch(dim3 grid, dim3 block, size_t smem, hipStream_t s, const Args &...args) {
+    static size_t allowed = 0;
+    if (smem > allowed) {
+        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        allowed = smem;
+    }
+    hipLaunchKernelGGL(KERNEL, grid, block, smem, s, args...);
+    EILEV_LAUNCH_CHECK();
+    return EILEV_OK;
+}
+
+// The runtime epilogue code (GemmArgs::epi: 0 none, 1 GELU, 2 ReLU) as a template argument: returns f(std::integral_constant<int, E>{}) for
+// the E of EPIS... that equals `epi`, and for the first of EPIS... when none does.  EPIS... are the instances a launcher has.
+template <int E0, int... EPIS, typename F>
+static inline int eilev_with_epi(int epi, F &&f) {
+    int rc = 0;
+    const bool hit = ((epi == EPIS && (rc = f(std::integral_constant<int, EPIS>{}), true)) || ...);
+    return hit ? rc : f(std::integral_constant<int, E0>{});
+}
 
 // Counter-based dropout mask (splitmix64 finaliser): the same function in the forward and the backward kernels and in the oracle,
 // so a mask is never stored.  keep iff hash >= p * 2^32.
@@ -214,6 +243,50 @@ __device__ __forceinline__ float gelu_erf_n1(float x) {
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---- probe bits ---------------------------------------------------------------------------------------------------------------
+// GemmArgs::dbg (eilev_debug_gemm_flags) and AttnArgs::dbg (eilev_debug_attn_v1(dbg << 1)) of the -DEILEV_PROBES build; always 0 in the
+// product library.  The values are an interface (tools/*.py and the A/B tests pass them as numbers): none may change.  Several share a bit
+// with a field (noted): both meanings apply.
+enum : int {
+    DBG_GEMM_ROW0_STORES = 1 << 0,          // epilogues store output row 0 only (and pp4 takes no lean epilogue)
+    DBG_GEMM_ONE_KSTEP = 1 << 1,            // K loops run one step
+    DBG_GEMM_NO_DMA = 1 << 2,               // register-staged per-tile kernels only: no LDS-DMA, pp4, w6, split-K or 64 x 128 route
+    DBG_GEMM_SKINNY_NO_DMA = 1 << 3,        // bf16 skinny launches: the plain kernel (no LDS-DMA, nb or rows32 kernels)
+    DBG_GEMM_FORCE_SHIFT = 4,               // (dbg >> 4) & 15: the tile choice forced (GemmForce below)
+    DBG_GEMM_SKINNY_NO_PRELOAD = 1 << 7,    // skinny kernels do not preload the activations (bit 3 of the force field)
+    DBG_GEMM_ROW_MAJOR_TILES = 1 << 8,      // tiles walked in plain row-major order (no XCD / group remap)
+    DBG_GEMM_NO_EPILOGUE = 1 << 10,         // no epilogue at all (accumulators kept alive)
+    DBG_GEMM_NO_STORES = 1 << 11,           // epilogue without its store phase
+    DBG_GEMM_A_ROW0 = 1 << 12,              // lda = 0: every A row aliases row 0
+    DBG_GEMM_W_ROW0 = 1 << 13,              // ldw = 0: every W row aliases row 0
+    DBG_GEMM_NO_WIDE = 1 << 14,             // 256 x 128 shapes are not promoted to the persistent kernels
+    DBG_GEMM_NO_STREAM_LAYOUT = 1 << 15,    // rows32 ignores GemmArgs::Wp
+    DBG_GEMM_C_ROW0 = 1 << 17,              // ldc = 0: every output row aliases row 0
+    DBG_GEMM_NO_HALF_TILES = 1 << 19,       // no 128-column half-tile path (pp4, tiled)
+    DBG_GEMM_WIDE_TILED = 1 << 20,          // a promoted 256 x 128 shape runs the per-tile 256 x 256 kernel, not pp4
+    DBG_GEMM_NO_W6 = 1 << 21,               // w6 is never picked
+    DBG_GEMM_GROUP_SHIFT = 22,              // (dbg >> 22) & 3: tile-group height 1: 4 rows, 2: 8, 3: 16
+    DBG_GEMM_PP4_NO_PRESTAGE = 1 << 24,     // pp4 without the lean epilogue and the second pre-staged K-step
+    DBG_GEMM_NB_SHIFT = 26,                 // (dbg >> 26) & 7: skinny weight blocks per workgroup 1 / 2 / 4 / (7) 8
+    DBG_GEMM_ROWS32_FIRST_FIT = 1 << 27,    // rows32 first-fit plan, GemmArgs::Wp ignored (bit 1 of the nb field)
+    DBG_GEMM_NO_ROWS32 = 1 << 28,           // rows32 never takes a launch (bit 2 of the nb field)
+    DBG_GEMM_NO_REDUCE_LN = 1 << 29,        // split-K reduce and LayerNorm as two launches
+    DBG_GEMM_NB_BLOCKS_ONLY = 1 << 30,      // the nb default counts weight blocks, not blocks x K splits
+
+    DBG_ATTN_NO_COMPUTE = 1 << 0,           // attn_prefill_v2_kernel stages its key tiles but computes nothing
+    DBG_ATTN_NO_PREFETCH = 1 << 1,          // attn_prefill_v2_kernel does not stage the next key tile early
+    DBG_ATTN_NO_FRAME = 1 << 2,             // no whole-frame ViT kernel
+    DBG_ATTN_FRAME3 = 1 << 4,               // the two-phase frame kernel at any frame count
+    DBG_ATTN_NO_FRAME3 = 1 << 5,            // never the two-phase frame kernel
+    DBG_ATTN_V2_4WAVES = 1 << 6,            // hd = 128: 4 waves per workgroup
+    DBG_ATTN_FRAME_STAMPS = 1 << 8,         // attn_frame_kernel phase stamps
+    DBG_ATTN_FRAME3_STAMPS = 1 << 9,        // attn_frame3_kernel phase stamps (and the two-phase kernel forced)
+    DBG_ATTN_HEAD_MAJOR = 1 << 10,          // TIMING (wrong results): q / k / v read as if stored head-major
+    DBG_ATTN_FRAME3_NO_STORES = 1 << 11,    // TIMING (no output): attn_frame3_kernel without its O stores
+};
+// (dbg >> DBG_GEMM_FORCE_SHIFT) & 15: 1-4 = that TileCfg (gemm.hip), or one kernel regardless of the shape
+enum GemmForce : int { FORCE_NONE = 0, FORCE_PP4 = 9, FORCE_W6 = 12, FORCE_64x128 = 13, FORCE_128x128 = 14, FORCE_SPLIT_K = 15 };
 
 // ---- host-side launchers shared between translation units -------------------------------------
 struct GemmArgs {

@@ -41,7 +41,7 @@ __device__ __forceinline__ void tile_coords(const GemmArgs &g, int tiles_m, int 
     const int nwg = tiles_m * tiles_n;
     const int xcd = t & 7, q = nwg >> 3, r = nwg & 7;
     t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (t >> 3);
-    if (g.dbg & 256) {  // probe: plain row-major order
+    if (g.dbg & DBG_GEMM_ROW_MAJOR_TILES) {  // probe: plain row-major order
         tm = t / tiles_n;
         tn = t % tiles_n;
         return;
@@ -53,7 +53,7 @@ __device__ __forceinline__ void tile_coords(const GemmArgs &g, int tiles_m, int 
     // half tiles last (every XCD in step on equal work) = fc2 1090 -> 983, proj 930 -> 880, qkv 1095 -> 1084 TFLOP/s — 256 half tiles
     // at once are fabric-bound (an A panel per 128 output columns); two half tiles as one unit = fc2 1123 -> 906-1003 (a 1.5-tile unit
     // per ~11 doubles the imbalance of the static stride).
-    const int gsel = (g.dbg >> 22) & 3;  // probe override: 1 -> 4 rows, 2 -> 8 rows, 3 -> 16 rows
+    const int gsel = (g.dbg >> DBG_GEMM_GROUP_SHIFT) & 3;  // probe override: 1 -> 4 rows, 2 -> 8 rows, 3 -> 16 rows
     const int GROUP_M = gsel == 1 ? 4 : gsel == 2 ? 8 : gsel == 3 ? 16 : (tiles_n <= 8 ? 4 : 8);
     const int width = GROUP_M * tiles_n, group = t / width, first = group * GROUP_M;
     const int gsz = min(tiles_m - first, GROUP_M), in = t - group * width;
@@ -86,7 +86,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[W
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int col = wcol0 + j * 32 + q * 8 + hi * 4;
-                    if (row < g.M && col < g.N && !((g.dbg & 1) && row > 0)) {
+                    if (row < g.M && col < g.N && !((g.dbg & DBG_GEMM_ROW0_STORES) && row > 0)) {
                         float *dst = reinterpret_cast<float *>(g.C) + (int64_t)row * g.ldc + col;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -108,7 +108,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[W
         }
         return;
     }
-    if (g.dbg & 1024) {  // probe: no epilogue at all (keep acc alive)
+    if (g.dbg & DBG_GEMM_NO_EPILOGUE) {  // probe: no epilogue at all (keep acc alive)
         float keep = 0.0f;
 #pragma unroll
         for (int i = IBEG; i < IEND; ++i)
@@ -126,7 +126,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[W
     const int wrow1 = wrow0 + IBEG * 32;            // first global row of this pass
     const int srow = lane >> 3, schunk = lane & 7;  // row-major phases: 8 lanes per 128-byte row segment
     const bool patch = g.patch_group > 0;
-    const bool interior = wrow1 + ROWS <= g.M && wcol0 + WN <= g.N && !patch && !(g.dbg & 1);
+    const bool interior = wrow1 + ROWS <= g.M && wcol0 + WN <= g.N && !patch && !(g.dbg & DBG_GEMM_ROW0_STORES);
     const bool has_res = g.resid != nullptr;
     const bool has_scale = g.scale_cols > 0;
     // (a) residual rows -> LDS
@@ -262,7 +262,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[W
                 *reinterpret_cast<float2 *>(g.stat_out + ((int64_t)(wcol0 >> 6) * g.stat_ld + row) * 2) = make_float2(t1, t2);
         }
     }
-    if (g.dbg & 2048) return;  // probe: no store phase
+    if (g.dbg & DBG_GEMM_NO_STORES) return;  // probe: no store phase
     // (c) rows -> HBM
     if (interior) {
         bf16 *dp = reinterpret_cast<bf16 *>(g.C) + (int64_t)(wrow1 + srow) * g.ldc + wcol0 + schunk * 8;
@@ -280,7 +280,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[W
 #pragma unroll 2
     for (int it = 0; it < ROWS / 8; ++it) {
         const int lr = it * 8 + srow, row = wrow1 + lr, col = wcol0 + schunk * 8;
-        if (row < g.M && col < g.N && !((g.dbg & 1) && row > 0)) {
+        if (row < g.M && col < g.N && !((g.dbg & DBG_GEMM_ROW0_STORES) && row > 0)) {
             const bf16x4 *sp = reinterpret_cast<const bf16x4 *>(reg + lr * RS + schunk * 16);
             const bf16x4 lo = sp[0], hi4 = sp[1];
             int64_t orow = row;

@@ -272,8 +272,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     const unsigned stg_sw16 = (unsigned)(STG0 + wid * 4096 + l15 * 128 + (g4 & 1) * 8) ^ (unsigned)((((g4 >> 1) ^ (l15 & 7)) << 4));
     const int srow = lane >> 3, schunk = lane & 7;
     auto is_lean = [&](int n0_) {
-        return !(n0_ + 128 >= g.N && !(g.dbg & 524288)) && n0_ + BN <= g.N && !g.out_f32 && g.patch_group == 0 && g.scale_cols == 0 && !g.wscale && !g.ascale &&
-               !(g.dbg & (1024 | 2048 | 1)) && !(g.dbg & 16777216);
+        return !(n0_ + 128 >= g.N && !(g.dbg & DBG_GEMM_NO_HALF_TILES)) && n0_ + BN <= g.N && !g.out_f32 && g.patch_group == 0 && g.scale_cols == 0 && !g.wscale && !g.ascale &&
+               !(g.dbg & (DBG_GEMM_NO_EPILOGUE | DBG_GEMM_NO_STORES | DBG_GEMM_ROW0_STORES)) && !(g.dbg & DBG_GEMM_PP4_NO_PRESTAGE);
     };
     // LN == 2 (proj / fc2, residual): the unit also emits the row statistics of what it writes (g.stat_out); LN == 1 (qkv / fc1, no residual):
     // (qkv / fc1) it finishes a folded LayerNorm (g.ln_rows / g.ln_csum): see GemmArgs.
@@ -533,9 +533,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     if (t >= ntiles) return;
     set_tile(t, m0, n0);
     // half tile: only W rows 0..127 of the tile exist; the late waves 6 and 7 (rows 128..255) have nothing to stage
-    auto w_piece_mine = [&](int n0_) { return !(n0_ + 128 >= g.N && !(g.dbg & 524288)) || wid < NW / 2 + 2; };
+    auto w_piece_mine = [&](int n0_) { return !(n0_ + 128 >= g.N && !(g.dbg & DBG_GEMM_NO_HALF_TILES)) || wid < NW / 2 + 2; };
     stage_step(0, w_piece_mine(n0));
-    bool pre1 = ns > 1 && (A3 || !(g.dbg & 16777216));  // step 1 of the coming tile is already staged (prologue / previous tile's tail)
+    bool pre1 = ns > 1 && (A3 || !(g.dbg & DBG_GEMM_PP4_NO_PRESTAGE));  // step 1 of the coming tile is already staged (prologue / previous tile's tail)
     if (pre1) stage_step(1, w_piece_mine(n0));
     bool lean_cur = M16 || is_lean(n0);  // this tile runs the lean epilogue (M16: every tile does)
     // folded LayerNorm (LN == 1): C = rstd * (A . W^T - mean * csum) + bias.  The rank-1 term -mean[m] * csum[n] is one more K-slice on
@@ -557,7 +557,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
 #pragma unroll
             for (int j = 0; j < TN16; ++j) ln_cl[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rcs, (nb + j * 16) * 4, 0, 0));
         } else if constexpr (LN == 1) {
-            const bool ht = n0_ + 128 >= g.N && !(g.dbg & 524288);
+            const bool ht = n0_ + 128 >= g.N && !(g.dbg & DBG_GEMM_NO_HALF_TILES);
             const int mb = m0_ + (ht ? hm * 64 : wm * WM) + l31, nb = n0_ + (ht ? hn * 64 : wn * WN) + l31;
             const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)g.ln_rows, 0, g.M * 8, 0x00020000);
             const __amdgpu_buffer_rsrc_t rcs = __builtin_amdgcn_make_buffer_rsrc((void *)g.ln_csum, 0, g.N * 4, 0x00020000);
@@ -661,8 +661,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
         PP_BARRIER();
         if (late) PP_BARRIER();
         stamp(1);
-        const int nsd = (g.dbg & 2) ? 1 : ns;
-        const bool half_tile = n0 + 128 >= g.N && !(g.dbg & 524288);
+        const int nsd = (g.dbg & DBG_GEMM_ONE_KSTEP) ? 1 : ns;
+        const bool half_tile = n0 + 128 >= g.N && !(g.dbg & DBG_GEMM_NO_HALF_TILES);
         // one K-step = two half-steps; FIRST (compile-time) marks the tile's first K-step, whose first 16 MFMAs take C = bias / 0
         // DMA schedule (round 3).  A step buffer is free once BOTH wave groups have read its second half; the early group (E) gets
         // there one barrier interval before the late group (L).  r2 issued step st + 1 in the read phase of half 0 of step st and

@@ -539,7 +539,7 @@ __global__ __launch_bounds__(256) void stream_pack_kernel(const bf16 *__restrict
 
 static bool rows32_plan(const GemmArgs &g, int nb, int n_cu, SkinnyArgs &a, int &ks, int &ksteps, int &grid_x) {
     int k5 = 0;
-    if (!rows32_shape(g.N, g.K, n_cu, k5, ksteps, grid_x, (g.dbg & 134217728) != 0)) return false;
+    if (!rows32_shape(g.N, g.K, n_cu, k5, ksteps, grid_x, (g.dbg & DBG_GEMM_ROWS32_FIRST_FIT) != 0)) return false;
     if (g.c_frag && (k5 > 1 || g.out_f32 || g.wscale || g.resid || (g.N & 31))) return false;  // c_frag: the plain bf16 epilogue only
     if (g.ln_frag && (k5 == 1 || !g.ln_out)) return false;                                      // ln_frag: the fused split-K reduce only
     if (g.a_frag && g.M > 32) return false;
@@ -554,7 +554,7 @@ static bool rows32_plan(const GemmArgs &g, int nb, int n_cu, SkinnyArgs &a, int 
     // The split-K forms (out_proj: 2 x 128 workgroups of 20 rows; fc2: 4 x 64 of 40 rows) lost to the round-3 kernels while the rows were dealt in
     // 16-row blocks (r4); with the rows dealt one by one every CU streams the same bytes and they win: 4.65 -> 4.50 ms / token at batch 32 (r5).
     // probe flag 1 << 27: the round-3 kernels for these shapes
-    if (k5 > 1 && (g.dbg & 134217728)) return false;
+    if (k5 > 1 && (g.dbg & DBG_GEMM_ROWS32_FIRST_FIT)) return false;
     if (k5 > 1 && (!g.scratch || (size_t)k5 * a.mr * g.N * sizeof(float) > g.scratch_bytes)) return false;
     ks = k5;
     a.ks = k5;

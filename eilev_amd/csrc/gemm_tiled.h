@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_nt_kernel(const GemmArgs 
     swrite(0);
     __syncthreads();
 
-    for (int kt = 0; kt < ((g.dbg & 2) ? 1 : nk); ++kt) {
+    for (int kt = 0; kt < ((g.dbg & DBG_GEMM_ONE_KSTEP) ? 1 : nk); ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < nk) gload(kt + 1);  // in flight while the MFMAs below run
         const char *sa = smem + cur * STAGE + (wm * WM) * 128;
@@ -205,12 +205,12 @@ __global__ __launch_bounds__(64 * NWM * NWN, MINW) void gemm_glds_kernel(const G
         }
         if (PRIO) __builtin_amdgcn_s_setprio(0);
     };
-    const int nkd = (g.dbg & 2) ? 1 : nk;
+    const int nkd = (g.dbg & DBG_GEMM_ONE_KSTEP) ? 1 : nk;
     // Half-empty last column tile (N % 256 <= 128, e.g. N = 1408 = 5.5 x 256): only columns [0, 128) of the tile exist.
     // Instead of letting the waves of the two right-hand column blocks multiply padding, the 8 waves re-split the valid
     // 256 x 128 region as 4 x 2 blocks of 64 x 64: half the MFMAs per wave, no DMA for the missing W rows.
     constexpr bool HALF_OK = BM == 256 && BN == 256 && NWM == 2 && NWN == 4 && NSTAGE == 2;
-    const bool half_tile = HALF_OK && n0 + 128 >= g.N && !(g.dbg & 524288);
+    const bool half_tile = HALF_OK && n0 + 128 >= g.N && !(g.dbg & DBG_GEMM_NO_HALF_TILES);
     if (HALF_OK && half_tile) {
         const int hm = wm * 2 + (wn >> 1), hn = wn & 1;  // 64-row block, 64-column block of this wave
         auto stage_half_tile = [&](int buf, int kt) {
@@ -284,30 +284,18 @@ __global__ __launch_bounds__(64 * NWM * NWN, MINW) void gemm_glds_kernel(const G
 
 template <int BM, int BN, int NWM, int NWN, int EPI, int NSTAGE, int MINW, int PRIO = 0>
 int launch_tiled_e(const GemmArgs &g, hipStream_t s) {
-    static bool attr_set = false;
     constexpr int stages = NSTAGE * (BM + BN) * 128, epi = NWM * NWN * (BM / NWM) * ((BN / NWN) * 2 + 8);
     constexpr int smem = stages > epi ? stages : epi;
     constexpr int smem_nt = 2 * (BM + BN) * 128 > epi ? 2 * (BM + BN) * 128 : epi;
-    const bool fast = (g.K % BK) == 0 && !(g.dbg & 4) && (int64_t)g.M * g.lda * 2 < 0x7fff0000ll && (int64_t)g.N * g.ldw * 2 < 0x7fff0000ll;
-    if (!attr_set) {
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_glds_kernel<BM, BN, NWM, NWN, EPI, NSTAGE, MINW, PRIO>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_nt_kernel<BM, BN, NWM, NWN, EPI>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, smem_nt));
-        attr_set = true;
-    }
+    const bool fast = (g.K % BK) == 0 && !(g.dbg & DBG_GEMM_NO_DMA) && (int64_t)g.M * g.lda * 2 < 0x7fff0000ll && (int64_t)g.N * g.ldw * 2 < 0x7fff0000ll;
     const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-    if (fast) hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, NWM, NWN, EPI, NSTAGE, MINW, PRIO>), dim3(tiles), dim3(64 * NWM * NWN), smem, s, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, NWM, NWN, EPI>), dim3(tiles), dim3(64 * NWM * NWN), smem_nt, s, g);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    if (fast) return eilev_launch<gemm_glds_kernel<BM, BN, NWM, NWN, EPI, NSTAGE, MINW, PRIO>>(dim3(tiles), dim3(64 * NWM * NWN), smem, s, g);
+    return eilev_launch<gemm_nt_kernel<BM, BN, NWM, NWN, EPI>>(dim3(tiles), dim3(64 * NWM * NWN), smem_nt, s, g);
 }
 
 template <int BM, int BN, int NWM, int NWN, int NSTAGE, int MINW, int PRIO = 0>
 int launch_tiled(const GemmArgs &g, hipStream_t s) {
-    if (g.epi == 1) return launch_tiled_e<BM, BN, NWM, NWN, 1, NSTAGE, MINW, PRIO>(g, s);
-    if (g.epi == 2) return launch_tiled_e<BM, BN, NWM, NWN, 2, NSTAGE, MINW, PRIO>(g, s);
-    return launch_tiled_e<BM, BN, NWM, NWN, 0, NSTAGE, MINW, PRIO>(g, s);
+    return eilev_with_epi<0, 1, 2>(g.epi, [&](auto e) { return launch_tiled_e<BM, BN, NWM, NWN, decltype(e)::value, NSTAGE, MINW, PRIO>(g, s); });
 }
 
 

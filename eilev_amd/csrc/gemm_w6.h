@@ -318,26 +318,11 @@ __global__ __launch_bounds__(256, 1) void gemm_w6_kernel(const GemmArgs g) {
 }
 
 int launch_w6(const GemmArgs &g, hipStream_t s) {
-    static bool attr_set = false;
-    static int num_cu = 0;
     constexpr int smem = 3 * 49152 + 4 * 4096;
-    if (!attr_set) {
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_w6_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_w6_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_w6_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int dev = 0;
-        EILEV_HIP_CHECK(hipGetDevice(&dev));
-        EILEV_HIP_CHECK(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        attr_set = true;
-    }
     const int tiles = ((g.M + 255) / 256) * ((g.N + 127) / 128);
-    const int ncu = eilev_grid_cus() < num_cu ? eilev_grid_cus() : num_cu;
+    const int ncu = eilev_grid_cus();
     const int grid = tiles < ncu ? tiles : ncu / 8 * 8;
-    if (g.epi == 1) hipLaunchKernelGGL(gemm_w6_kernel<1>, dim3(grid), dim3(256), smem, s, g);
-    else if (g.epi == 2) hipLaunchKernelGGL(gemm_w6_kernel<2>, dim3(grid), dim3(256), smem, s, g);
-    else hipLaunchKernelGGL(gemm_w6_kernel<0>, dim3(grid), dim3(256), smem, s, g);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    return eilev_with_epi<0, 1, 2>(g.epi, [&](auto e) { return eilev_launch<gemm_w6_kernel<decltype(e)::value>>(dim3(grid), dim3(256), smem, s, g); });
 }
 
 

@@ -205,14 +205,7 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const GemvArgs a) {
 
 template <int MR, int PRO, int CPS>
 int launch_rows_c(const GemvArgs &a, int grid, size_t smem, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemv_rows_kernel<MR, PRO, CPS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
-    hipLaunchKernelGGL((gemv_rows_kernel<MR, PRO, CPS>), dim3(grid), dim3(256), smem, s, a);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    return eilev_launch<gemv_rows_kernel<MR, PRO, CPS>>(dim3(grid), dim3(256), smem, s, a);
 }
 
 template <int MR, int PRO>
@@ -610,17 +603,9 @@ int launch_gemvm_c(const GemvArgs &a, int grid, hipStream_t s) {
     // of all slots and spills (MR = 5, 8 slots: 862 VGPRs spilled), so 4 there
     constexpr int RB = (PRO == PRO_LN || MR >= 3) ? 4 : 8;
     const size_t smem = (size_t)MR * NCH * 512 * sizeof(bf16);
-    static bool attr = false;
-    if (!attr) {
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemvm_kernel<MR, NCH, PRO, SB, RB, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        EILEV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemvm_kernel<MR, NCH, PRO, SB, RB, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
     // one code path per instance (both in one kernel doubled the register pressure): long waves only when EVERY wave has 2 RB items
-    if (a.rows_per_wave * IPR >= 2 * RB) hipLaunchKernelGGL((gemvm_kernel<MR, NCH, PRO, SB, RB, true>), dim3(grid), dim3(320), smem, s, a);
-    else hipLaunchKernelGGL((gemvm_kernel<MR, NCH, PRO, SB, RB, false>), dim3(grid), dim3(320), smem, s, a);
-    EILEV_LAUNCH_CHECK();
-    return EILEV_OK;
+    if (a.rows_per_wave * IPR >= 2 * RB) return eilev_launch<gemvm_kernel<MR, NCH, PRO, SB, RB, true>>(dim3(grid), dim3(320), smem, s, a);
+    return eilev_launch<gemvm_kernel<MR, NCH, PRO, SB, RB, false>>(dim3(grid), dim3(320), smem, s, a);
 }
 template <int NCH, int PRO>
 int launch_gemvm_m(const GemvArgs &a, int grid, hipStream_t s) {
