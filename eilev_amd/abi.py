@@ -513,6 +513,54 @@ def use_probes() -> None:
     _hip, HIP_LIB_PATH = lib, PROBES_LIB_PATH
 
 
+# ---- the prompt-lookup decoding companion library (include/eilev_pld.h): a second shared library with its own exports, loaded on demand ----
+PLD_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_pld.so")
+PLD_ABI_VERSION = 1
+PLD_MAX_K = 64
+PLD_MAX_EOS = 8
+PLD_EXPORTS = ["eilev_pld_abi_version", "eilev_pld_draft", "eilev_pld_scratch_bytes", "eilev_pld_step"]
+
+
+class PldParams(C.Structure):
+    _fields_ = [("k", C.c_int64), ("ngram", C.c_int64), ("max_new", C.c_int64), ("slot_base", C.c_int64), ("slot_limit", C.c_int64),
+                ("corpus_cap", C.c_int64), ("n_eos", C.c_int64), ("eos", C.c_int64 * PLD_MAX_EOS)]
+
+
+def pld_params(k, ngram, max_new, slot_base, slot_limit, corpus_cap, eos_ids) -> PldParams:
+    eos_ids = [int(e) for e in eos_ids]
+    if len(eos_ids) > PLD_MAX_EOS:
+        raise NotImplementedError(f"prompt lookup takes at most {PLD_MAX_EOS} EOS ids")
+    p = PldParams(int(k), int(ngram), int(max_new), int(slot_base), int(slot_limit), int(corpus_cap), len(eos_ids))
+    for i, e in enumerate(eos_ids):
+        p.eos[i] = e
+    return p
+
+
+_pld = None
+
+
+def load_pld() -> C.CDLL:
+    """Load libeilev_hip_pld.so (built next to libeilev_hip.so by build_hip()).  No fallback: a missing build is an error."""
+    global _pld
+    if _pld is None:
+        if not os.path.exists(PLD_LIB_PATH):
+            raise RuntimeError(f"{PLD_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(PLD_LIB_PATH)
+        i64, i32, sz = C.c_int64, C.c_int, C.c_size_t
+        PP = C.POINTER(PldParams)
+        lib.eilev_pld_abi_version.restype = i32
+        lib.eilev_pld_scratch_bytes.restype = sz
+        lib.eilev_pld_scratch_bytes.argtypes = [i64, i64]
+        lib.eilev_pld_draft.restype = i32
+        lib.eilev_pld_draft.argtypes = [PP, vp, vp, vp, vp, vp]
+        lib.eilev_pld_step.restype = i32
+        lib.eilev_pld_step.argtypes = [PP, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        if lib.eilev_pld_abi_version() != PLD_ABI_VERSION:
+            raise RuntimeError(f"{PLD_LIB_PATH}: ABI version mismatch")
+        _pld = lib
+    return _pld
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         names = {-1: "EILEV_E_BADARG", -2: "EILEV_E_UNSUPPORTED", -3: "EILEV_E_WORKSPACE"}

@@ -1,4 +1,5 @@
-"""Builds eilev_amd/csrc/libeilev_hip.so (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
+"""Builds eilev_amd/csrc/libeilev_hip.so and its prompt-lookup companion libeilev_hip_pld.so (gfx950) in-tree with hipcc.
+Cross-compiles without a GPU."""
 from __future__ import annotations
 
 import os
@@ -12,6 +13,10 @@ HEADERS = ["common.h", "gemm_common.h", "gemm_tiled.h", "gemm_pp4.h", "gemm_w6.h
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"]
 LIB = os.path.join(HERE, "libeilev_hip.so")
+# the prompt-lookup decoding companion (include/eilev_pld.h): its own source, header and version script; it does not link the core library
+PLD_SOURCE = "pld.hip"
+PLD_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_pld.h")]
+PLD_LIB = os.path.join(HERE, "libeilev_hip_pld.so")
 
 
 def _hipcc() -> str:
@@ -54,8 +59,20 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "", ext
             raise RuntimeError(f"hipcc failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
         return r.stderr
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES) + 1) as ex:
+    # the default build (no variant) also builds the companion library; the probe variant does not need it
+    pld_src, pld_map = os.path.join(HERE, PLD_SOURCE), os.path.join(HERE, "exports_pld.map")
+    pld_deps = [pld_src, pld_map] + [os.path.join(HERE, h) for h in PLD_HEADERS]
+    pld_job = None
+    if not variant and (force or _stale(PLD_LIB, pld_deps)):
+        pld_job = [_hipcc(), *FLAGS, *extra_flags, "-shared", "-o", PLD_LIB, pld_src, "-Wl,--version-script=" + pld_map]
+
+    with ThreadPoolExecutor(max_workers=len(SOURCES) + 2) as ex:
+        pld_fut = ex.submit(run, pld_job) if pld_job else None
         for warn in ex.map(run, jobs):
+            if verbose and warn.strip():
+                print(warn, file=sys.stderr)
+        if pld_fut is not None:
+            warn = pld_fut.result()
             if verbose and warn.strip():
                 print(warn, file=sys.stderr)
     if force or jobs or _stale(lib, objs + [os.path.join(HERE, "exports.map")]):

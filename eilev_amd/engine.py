@@ -719,6 +719,86 @@ class HipEngine:
         return (ids, step_logits) if return_step_logits else ids
 
 
+    def _pld_buffers(self, text_ids, max_new_tokens, k, vocab):
+        """Device state of one prompt-lookup generation (include/eilev_pld.h): corpus (text ids, room for max_new ids), its length, the
+        window [last, d1 .. dk], the decode step's state words, the output ids, the status block, the arg-max scratch, the window logits."""
+        pld = abi.load_pld()
+        text = text_ids.to(self.device, torch.int64).reshape(-1)
+        n_text = int(text.numel())
+        b = dict(corpus=torch.zeros(n_text + max_new_tokens, dtype=torch.int64, device=self.device),
+                 corpus_len=torch.full((1,), n_text, dtype=torch.int32, device=self.device),
+                 window=torch.zeros(k + 1, dtype=torch.int64, device=self.device),
+                 state=torch.zeros(2, dtype=torch.int32, device=self.device),
+                 out=torch.zeros(max_new_tokens, dtype=torch.int64, device=self.device),
+                 status=torch.zeros(4, dtype=torch.int32, device=self.device),
+                 scratch=torch.empty(int(pld.eilev_pld_scratch_bytes(k + 1, vocab)), dtype=torch.uint8, device=self.device),
+                 logits=torch.empty((k + 1, vocab), dtype=torch.float32, device=self.device))
+        b["corpus"][:n_text] = text
+        return pld, b, n_text
+
+    def _pld_commit(self, pld, params, b, logits, rows, vocab):
+        abi.check(pld.eilev_pld_step(C.byref(params), _ptr(logits), rows, vocab, _ptr(b["corpus"]), _ptr(b["corpus_len"]), _ptr(b["window"]),
+                                     _ptr(b["state"]), _ptr(b["out"]), _ptr(b["status"]), _ptr(b["scratch"]), b["scratch"].numel(),
+                                     self._stream()), "eilev_pld_step")
+        return b["status"].tolist()  # the one read-back of the step
+
+    def greedy_lookup_decode(self, inputs_embeds, attention_mask, text_ids, max_new_tokens, num_tokens=10, ngram=2, eos_id=-1, pad_id=1, trace=None):
+        """Greedy decoding with prompt-lookup drafts [hf generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=n), batch 1]:
+        returns the ids of greedy_decode, int64 (1, n) of NEW tokens.  ``text_ids``: the row's visible text ids (no left padding, no
+        video placeholder), the corpus the drafts are looked up in together with the committed ids.  ``eos_id``: an id, a list of
+        ids, or < 0.  The prompt is prefilled once; each step verifies [last, d1 .. dm] with eilev_opt_extend, or runs the plain
+        decode step when there is no draft; libeilev_hip_pld.so commits and drafts.  No hipGraph: the shapes change per step.
+        Counters of the call: ``self.pld_stats``.  ``trace``: a list that receives a copy of the logits every commit read (tests)."""
+        from .pld import lookup_loop
+        from .sampling import eos_list
+
+        d = self.dims
+        B, L, _ = inputs_embeds.shape
+        if B != 1:
+            raise ValueError("assisted generate is only supported for batch_size = 1")
+        k, n_new = int(num_tokens), int(max_new_tokens)
+        if not 1 <= k <= abi.PLD_MAX_K or int(ngram) < 1:
+            raise ValueError(f"prompt_lookup_num_tokens must be in 1..{abi.PLD_MAX_K} and max_matching_ngram_size >= 1")
+        self.pld_stats = dict(verify=0, single=0, accepted=0)
+        if n_new <= 0:
+            return torch.empty((1, 0), dtype=torch.int64, device=self.device)
+        eos = eos_list(eos_id)
+        cap = L + n_new + k
+        pld, b, n_text = self._pld_buffers(text_ids, n_new, k, d.vocab)
+        params = abi.pld_params(k, ngram, n_new, L, min(cap, d.max_pos), n_text + n_new, eos)
+        am = attention_mask.to(self.device, torch.int32).reshape(1, L).contiguous()
+        full = torch.ones((1, cap), dtype=torch.int32, device=self.device)  # [prompt mask, ones]: every verify window reads a prefix
+        full[:, :L] = am
+        n_valid = am.sum(dim=1, dtype=torch.int32)
+        finished = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        kv = self.new_kv_cache(1, cap)
+        emb = torch.empty((1, k + 1, d.t_hidden), dtype=torch.bfloat16, device=self.device)
+        ws = self._workspace("pld", self.lib.eilev_opt_workspace_bytes(C.byref(d), 1, cap))
+        ws1 = self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), 1, 1))
+        window, logits, state, out = b["window"], b["logits"], b["state"], b["out"]
+        last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
+
+        def verify(c, m):
+            abi.check(self.lib.eilev_embed_scatter(C.byref(d), self.pack.embed_tokens, _ptr(window), None, None, 0, 1, m + 1, _ptr(emb),
+                                                   self._stream()), "eilev_embed_scatter")
+            abi.check(self.lib.eilev_opt_extend(C.byref(d), C.byref(self.pack.opt), _ptr(emb), _ptr(full), 1, m + 1, L + c - 1, _ptr(kv), cap,
+                                                _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_opt_extend")
+            return logits
+
+        def single(c):  # state[0] == c and window[0] == the last committed id: the plain greedy step, its arithmetic and its KV slot
+            abi.check(self.lib.eilev_opt_decode_step(C.byref(d), C.byref(self.pack.opt), _ptr(window), _ptr(state), _ptr(am), _ptr(n_valid), 1, L,
+                                                     _ptr(kv), cap, _ptr(logits), _ptr(finished), -1, int(pad_id), _ptr(out), n_new, _ptr(ws1),
+                                                     ws1.numel(), self._stream()), "eilev_opt_decode_step")
+            return logits
+
+        def commit(lg, rows):
+            if trace is not None:
+                trace.append(lg[:rows].clone())
+            return self._pld_commit(pld, params, b, lg, rows, d.vocab)
+
+        c = lookup_loop(commit(last, 1), verify, single, commit, self.pld_stats)  # the first id: the prefill's last logits
+        return out[:c].reshape(1, c).clone()
+
     def beam_decode(self, inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty=1.0, eos_id=-1, pad_id=1,
                     early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, use_graph=True, trace=None, rules=None):
         """Beam search on the HIP path [sample default: num_beams=5, length_penalty=-1; hf generation/utils.py:3208+].
@@ -1014,6 +1094,51 @@ class HipEngine:
             ids = ids[:, : int(first.max().item())]
         start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
         return torch.cat((start, ids), dim=1)
+
+    def t5_greedy_lookup(self, inputs_embeds, attention_mask, text_ids, max_new_tokens, num_tokens=10, ngram=2, eos_id=1, pad_id=0, start_id=0):
+        """t5_greedy with prompt-lookup drafts (batch 1): returns the decoder ids of t5_greedy, start id included.  The corpus is the
+        encoder's text ids (``text_ids``), then the generated decoder ids.  Each step verifies [last, d1 .. dm] with eilev_t5_decode
+        (past_len = committed count) or runs eilev_t5_decode_step when there is no draft.  Counters of the call: ``self.pld_stats``."""
+        from .pld import lookup_loop
+        from .sampling import eos_list
+
+        d = self.t5dims
+        B = inputs_embeds.shape[0]
+        if B != 1:
+            raise ValueError("assisted generate is only supported for batch_size = 1")
+        k, n_new = int(num_tokens), int(max_new_tokens)
+        if not 1 <= k <= abi.PLD_MAX_K or int(ngram) < 1:
+            raise ValueError(f"prompt_lookup_num_tokens must be in 1..{abi.PLD_MAX_K} and max_matching_ngram_size >= 1")
+        self.pld_stats = dict(verify=0, single=0, accepted=0)
+        enc = self.t5_encode(inputs_embeds, attention_mask)
+        ckv = self.t5_cross_kv(enc)
+        L = enc.shape[1]
+        start = torch.full((1, 1), int(start_id), dtype=torch.int64, device=self.device)
+        if n_new <= 0:
+            return start
+        cap = n_new + k
+        pld, b, n_text = self._pld_buffers(text_ids, n_new, k, d.vocab)
+        params = abi.pld_params(k, ngram, n_new, 1, cap, n_text + n_new, eos_list(eos_id))
+        am = attention_mask.to(self.device, torch.int32).contiguous()
+        skv = torch.empty(int(self.lib.eilev_t5_self_kv_bytes(C.byref(d), 1, cap)), dtype=torch.uint8, device=self.device)
+        ws = self._workspace("t5pld", self.lib.eilev_t5_workspace_bytes(C.byref(d), 1, k + 1, max(L, cap)))
+        window, logits, state, out = b["window"], b["logits"], b["state"], b["out"]
+        window[0] = int(start_id)
+
+        def verify(c, m):
+            abi.check(self.lib.eilev_t5_decode(C.byref(d), C.byref(self.pack.t5), _ptr(window), _ptr(am), 1, m + 1, c, _ptr(skv), cap, _ptr(ckv), L,
+                                               _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_t5_decode")
+            return logits
+
+        def single(c):  # state[0] == c tokens fed, window[0] == the next one to feed
+            abi.check(self.lib.eilev_t5_decode_step(C.byref(d), C.byref(self.pack.t5), _ptr(window), _ptr(state), _ptr(am), 1, _ptr(skv), cap,
+                                                    _ptr(ckv), L, _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_t5_decode_step")
+            return logits
+
+        abi.check(pld.eilev_pld_draft(C.byref(params), _ptr(b["corpus"]), _ptr(b["corpus_len"]), _ptr(window), _ptr(b["status"]), self._stream()),
+                  "eilev_pld_draft")
+        c = lookup_loop(b["status"].tolist(), verify, single, lambda lg, rows: self._pld_commit(pld, params, b, lg, rows, d.vocab), self.pld_stats)
+        return torch.cat((start, out[:c].reshape(1, c)), dim=1)
 
     def t5_beam(self, inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty=1.0, eos_id=1, pad_id=0, start_id=0,
                 early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, rules=None):

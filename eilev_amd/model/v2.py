@@ -569,6 +569,26 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             rules = dict(processors=procs if len(procs) else None, stopping=crit if len(crit) else None)
             if had_eos and not eos_ids:  # the EOS list was emptied above, the model still has an EOS id: hf fills shortened hypotheses with the pad id
                 rules["fill_id"] = int(pad)
+        # prompt-lookup decoding [hf generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=n)]: greedy search at batch 1 whose
+        # drafts are looked up in the prompt's text ids and the generated ids (eilev_amd/pld.py); checked here, before any encode
+        lookup = kw.pop("prompt_lookup_num_tokens", None)
+        lookup_ngram = 2
+        if lookup is not None:
+            lookup_ngram = kw.pop("max_matching_ngram_size", None)
+            lookup_ngram = 2 if lookup_ngram is None else int(lookup_ngram)  # hf generation/configuration_utils.py default
+            lookup = int(lookup)
+            if lookup < 1 or lookup_ngram < 1:
+                raise ValueError("prompt_lookup_num_tokens and max_matching_ngram_size must be >= 1")
+            if input_ids is not None and input_ids.shape[0] > 1:
+                raise ValueError("assisted generate is only supported for batch_size = 1")
+            combo = [n for n, on in (("num_beams > 1", num_beams > 1), ("do_sample=True", do_sample), ("logits processors", len(procs) > 0),
+                                     ("stopping criteria", len(crit) > 0), ("min_new_tokens", min_new > 0)) if on]
+            if combo:
+                raise NotImplementedError(f"prompt_lookup_num_tokens with {', '.join(combo)} is not built on the HIP path (greedy search only)")
+            if want_scores or want_logits:
+                raise NotImplementedError("generate(output_scores / output_logits) is served for greedy search on the decoder-only language model only")
+            if len(eos_ids) > 8:
+                raise NotImplementedError("prompt_lookup_num_tokens takes at most 8 EOS ids")
         if kw:
             raise NotImplementedError(f"unsupported generate() arguments on the HIP path: {sorted(kw)}")
         if want_dict and not (want_scores or want_logits):  # sequences only: any decoding mode, wrapped like hf wraps it
@@ -593,6 +613,17 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         eos1 = eos_ids[0] if eos_ids else -1
         host_rules = len(eos_ids) > 1 or min_new > 0 or rules is not None
         eng = self.engine()
+        if lookup is not None:  # the corpus: the row's visible text ids (no left padding, no video placeholder)
+            keep = attention_mask[0] != 0
+            if video_input_mask is not None:
+                keep = keep & (video_input_mask[0] == 0)
+            text = input_ids[0][keep.to(input_ids.device)]
+            if self._is_t5:
+                t = self.config.text_config
+                start = t.decoder_start_token_id if t.decoder_start_token_id is not None else t.pad_token_id
+                return eng.t5_greedy_lookup(emb, attention_mask, text, int(max_new), lookup, lookup_ngram, eos_id=eos_ids, pad_id=int(pad),
+                                            start_id=int(start))
+            return eng.greedy_lookup_decode(emb, attention_mask, text, int(max_new), lookup, lookup_ngram, eos_id=eos_ids, pad_id=int(pad))
         if want_dict:
             plain_greedy = num_beams == 1 and sampler is None and not host_rules
             if (want_scores or want_logits) and not (plain_greedy and not self._is_t5):
