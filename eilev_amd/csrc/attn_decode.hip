@@ -1,0 +1,616 @@
+// attn_decode.hip — single-query attention of a decode step against the KV cache: the flash-decoding split kernel and its merge, the
+// one-pass and 128-key-range kernels of small batches, the per-head loop of larger ones, and their launchers (common.h DecodeAttnArgs).
+#include "common.h"
+
+namespace {
+
+// ---- single-query attention against the cache (decode step) ---------------------------------------------
+// Flash-decoding split: grid (heads, batch, nsplit); each workgroup owns KEYS_PER_WG = 256 consecutive cache
+// slots of one (batch, head) and writes an un-normalised partial (max, sum, o[hd]) to `part`; a second tiny
+// kernel merges the splits.  kv_total = seq_len + state[0] is read on the device (hipGraph replay); keys
+// < seq_len obey attn_mask, newer ones are visible.  One key per thread for the scores (its whole K row:
+// hd/8 independent 16-byte loads in flight), thread = (key subset, d chunk) for p.V; HBM-bound.
+constexpr int DEC_KEYS = 256;
+
+// T5 use: state == nullptr (kv_total = seq_len, given by the host), attn_mask may be null (every key visible), ldq = row
+// stride of the query rows, rel_tab = per-head relative position bias over (key - query position), query at kv_total - 1.
+__global__ __launch_bounds__(256) void attn_decode_split_kernel(const bf16 *__restrict__ qkv, const bf16 *__restrict__ kc,
+                                                                const bf16 *__restrict__ vc, float *__restrict__ part,
+                                                                const int32_t *__restrict__ attn_mask,
+                                                                const int32_t *__restrict__ state, int seq_len, int cap,
+                                                                int heads, int hd, int64_t ldq, const float *__restrict__ rel_tab,
+                                                                int64_t rel_hs, int rel_off, int fuse_new,
+                                                                const bf16 *__restrict__ kg = nullptr, const bf16 *__restrict__ vg = nullptr,
+                                                                const int32_t *__restrict__ anc = nullptr, int beams = 1, int cap_g = 0,
+                                                                int rows = 0) {
+    // Beam search without moving the cache (anc != nullptr; eilev_opt_decode_step_beam): row b is beam b % beams of sample b / beams.
+    // Keys [0, seq_len) are the sample's PROMPT, held once in the prefill cache (kc / vc: `cap` = its capacity, row = sample); key
+    // seq_len + g is the g-th generated token of the hypothesis, written by whichever row held that hypothesis when it was generated:
+    // physical row anc[g * rows + b] of the generation cache (kg / vg, capacity cap_g).  The new token goes to this row's own slot.
+    __shared__ __attribute__((aligned(16))) float qs[128];
+    __shared__ float sc[DEC_KEYS];
+    __shared__ float red[DEC_KEYS * 17];  // per-key chunk partials (stride 17), later the p.V partials (nks * hd <= 2048)
+    __shared__ float wred[4];
+    __shared__ float bc[2];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y, sp = blockIdx.z, nsplit = gridDim.z;
+    const int d = heads * hd, nch = hd >> 3;
+    const int kv_total = anc ? min(seq_len + cap_g, seq_len + state[0]) : min(cap, seq_len + (state ? state[0] : 0));
+    const int k0 = sp * DEC_KEYS, k1 = min(kv_total, k0 + DEC_KEYS);
+    const int srow = anc ? b / beams : b;  // row of the prompt cache and of the attention mask
+    float *po = part + (((int64_t)b * heads + h) * nsplit + sp) * (hd + 2);
+    if (k0 >= kv_total) {  // nothing in this split yet
+        if (tid == 0) {
+            po[0] = -1e30f;
+            po[1] = 0.0f;
+        }
+        return;
+    }
+    const bf16 *kbase = kc + ((int64_t)srow * heads + h) * cap * hd;
+    const bf16 *vbase = vc + ((int64_t)srow * heads + h) * cap * hd;
+    auto key_row = [&](const bf16 *base, const bf16 *gen, int j) -> const bf16 * {
+        if (!anc || j < seq_len) return base + (int64_t)j * hd;
+        const int gi = j - seq_len;
+        int a = anc[(int64_t)gi * rows + b];  // a table entry outside [0, rows) must not become an address (the host fills it: ADVICE r3)
+        a = a < 0 ? 0 : (a >= rows ? rows - 1 : a);
+        return gen + (((int64_t)a * heads + h) * cap_g + gi) * hd;
+    };
+    if (tid < hd) qs[tid] = (float)qkv[(int64_t)b * ldq + h * hd + tid];
+    // fuse_new: the newest key / value (slot kv_total - 1) is still only in the q|k|v row of this step.  The split that owns the
+    // slot reads it from there and stores it into the cache (what a separate kv_write launch did before the attention).
+    // beam form: state[0] counts the generated tokens INCLUDING this step's, so it is >= 1 here; a caller that passes 0 (or more than the
+    // generation cache holds: kv_total is clamped above) must not make this row write outside its own generation slots
+    const int slot_raw = fuse_new ? kv_total - 1 : -1;
+    const int slot_new = (anc && (slot_raw < seq_len || state[0] > cap_g)) ? -1 : slot_raw;
+    const bf16 *knew = qkv + (int64_t)b * ldq + d + h * hd, *vnew = knew + d;
+    if (slot_new >= k0 && slot_new < k1 && tid < 2 * nch) {
+        const int which = tid / nch, cc = tid - which * nch;
+        bf16 *dst = anc ? const_cast<bf16 *>(which ? vg : kg) + (((int64_t)b * heads + h) * cap_g + (slot_new - seq_len)) * hd + cc * 8
+                        : const_cast<bf16 *>(which ? vbase : kbase) + (int64_t)slot_new * hd + cc * 8;
+        *reinterpret_cast<bf16x8 *>(dst) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
+    }
+    __syncthreads();
+
+    // scores: thread = (key subset ks, d chunk c) so that consecutive lanes read consecutive 16-byte chunks (a K row is
+    // hd * 2 = 160 contiguous bytes); the nch partial dot products of a key meet in LDS, then thread t owns key k0 + t
+    const int nks = 256 / nch;
+    const int c = tid % nch, ks = tid / nch;
+    const int nkeys = k1 - k0;
+    if (ks < nks) {
+        const float4 q0 = *reinterpret_cast<const float4 *>(&qs[c * 8]);
+        const float4 q1 = *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]);
+#pragma unroll 4
+        for (int jj = ks; jj < nkeys; jj += nks) {
+            float kv[8];
+            unpack8(*reinterpret_cast<const bf16x8 *>((k0 + jj == slot_new ? knew : key_row(kbase, kg, k0 + jj)) + c * 8), kv);
+            red[jj * 17 + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
+        }
+    }
+    __syncthreads();
+    const int j = k0 + tid;
+    float s = -1e30f;
+    if (j < k1) {
+        float acc = 0.0f;
+        for (int cc = 0; cc < nch; ++cc) acc += red[tid * 17 + cc];
+        const bool vis = j >= seq_len || !attn_mask || attn_mask[(int64_t)srow * seq_len + j] != 0;
+        if (rel_tab) acc += rel_tab[(int64_t)h * rel_hs + (rel_off >= 0 ? (j - (kv_total - 1)) + rel_off : j)];  // rel_off < 0: table of this query row
+        s = vis ? acc : -1e30f;
+    }
+    float mxw = wave_max(s);
+    if (lane == 0) wred[wid] = mxw;
+    __syncthreads();
+    const float mx = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
+    const float p = s > -1e29f ? __expf(s - mx) : 0.0f;
+    sc[tid] = (float)(bf16)p;  // P rounded to bf16 like the prefill kernel's MFMA operand
+    float sw = wave_sum(p);
+    __syncthreads();
+    if (lane == 0) wred[wid] = sw;
+    __syncthreads();
+    const float lsum = wred[0] + wred[1] + wred[2] + wred[3];
+
+    // p.V: same (ks, c) mapping
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+    if (ks < nks) {
+#pragma unroll 4
+        for (int jj = ks; jj < nkeys; jj += nks) {
+            float vv[8];
+            unpack8(*reinterpret_cast<const bf16x8 *>((k0 + jj == slot_new ? vnew : key_row(vbase, vg, k0 + jj)) + c * 8), vv);
+            const float pj = sc[jj];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[ks * hd + c * 8 + e] = acc[e];
+    }
+    __syncthreads();
+    if (tid < hd) {
+        float v = 0.0f;
+        for (int k2 = 0; k2 < nks; ++k2) v += red[k2 * hd + tid];
+        po[2 + tid] = v;
+    }
+    if (tid == 0) {
+        po[0] = mx;
+        po[1] = lsum;
+    }
+}
+
+// ---- small-batch form (round 4): ONE workgroup per (row, head), every key in one pass, no partials, no merge -------------------------------
+// At batch 1 the split kernel above costs 13.9 us per block for 9.8 MB of keys and values (profiles/r04_decode_b1_kernel_stats.md): 128
+// workgroups each walk three dependent load rounds, and the merge of their partials was repeated by every workgroup of out_proj.  Here a
+// 1024-thread workgroup owns a head: thread j requests key j's whole row (NCH 16-byte loads) AND its share of V (thread (kg, c): chunk c of
+// keys kg, kg + G, ... — VK loads) before anything is computed, so the head's K and V (307 KB at 960 keys x 80) arrive in one round trip;
+// scores, a block-wide softmax (P rounded to bf16 for the product like every attention kernel here, the row sum from the unrounded
+// values), p . V through LDS partials, the normalised row straight to `out`.  The new token's K / V come from the q|k|v row and are
+// stored to the cache here (fuse_new of the split kernel).  Needs cap <= 1024 and cap <= VK * (1024 / NCH).
+template <int NCH, int VK>
+__global__ __launch_bounds__(1024) void attn_decode1_kernel(const bf16 *__restrict__ qkv, bf16 *__restrict__ kc, bf16 *__restrict__ vc,
+                                                            bf16 *__restrict__ out, const int32_t *__restrict__ attn_mask,
+                                                            const int32_t *__restrict__ state, int seq_len, int cap, int heads, int64_t ldq) {
+    constexpr int hd = NCH * 8, G = 1024 / NCH, RS = NCH + 1;  // RS: row stride of the per-key chunk partials (odd: conflict-free column sums)
+    __shared__ __attribute__((aligned(16))) float qs[128];
+    __shared__ float ps[1024];
+    __shared__ float wred[32];
+    __shared__ float red[1024 * RS];  // scores: [key][chunk] partial dot products; afterwards the p . V partials [key group][hd] (G * hd <= 1024 * 8)
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y, d = heads * hd;
+    const int kv_total = min(cap, seq_len + state[0]);
+    const int slot_new = kv_total - 1;
+    bf16 *kbase = kc + ((int64_t)b * heads + h) * cap * hd, *vbase = vc + ((int64_t)b * heads + h) * cap * hd;
+    const bf16 *knew = qkv + (int64_t)b * ldq + d + h * hd, *vnew = knew + d;
+    // every load of the workgroup is requested here.  Thread (kg, c) owns 16-byte chunk c of keys kg, kg + G, ...: consecutive lanes read
+    // consecutive bytes (one key row per thread touches 64 cache lines per instruction and re-fetches each of them NCH times: 15 us)
+    const int c = tid % NCH, kg = tid / NCH;
+    bf16x8 kr[VK], vr[VK];
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        int key = kg + i * G;
+        key = key < kv_total ? key : slot_new;
+        kr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? knew : kbase + (int64_t)key * hd) + c * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        int key = kg + i * G;
+        key = key < kv_total ? key : slot_new;
+        vr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? vnew : vbase + (int64_t)key * hd) + c * 8);
+    }
+    const bool vis = tid < kv_total && (tid >= seq_len || !attn_mask || attn_mask[(int64_t)b * seq_len + tid] != 0);
+    if (tid < hd) qs[tid] = (float)qkv[(int64_t)b * ldq + h * hd + tid];
+    if (tid >= 1024 - 2 * NCH) {  // the new token's K / V -> the cache (what a separate kv_write launch did)
+        const int t2 = tid - (1024 - 2 * NCH), which = t2 / NCH, cc = t2 - which * NCH;
+        *reinterpret_cast<bf16x8 *>((which ? vbase : kbase) + (int64_t)slot_new * hd + cc * 8) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
+    }
+    __syncthreads();
+    if (kg < G) {
+        const float4 q0 = *reinterpret_cast<const float4 *>(&qs[c * 8]), q1 = *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]);
+#pragma unroll
+        for (int i = 0; i < VK; ++i) {
+            const int key = kg + i * G;
+            float kv[8];
+            unpack8(kr[i], kv);
+            if (key < 1024)
+                red[key * RS + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
+        }
+    }
+    __syncthreads();
+    float s = 0.0f;
+#pragma unroll
+    for (int cc = 0; cc < NCH; ++cc) s += red[tid * RS + cc];
+    s = vis ? s : -1e30f;
+    const float mxw = wave_max(s);
+    if (lane == 0) wred[wid] = mxw;
+    __syncthreads();
+    float mx = wred[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) mx = fmaxf(mx, wred[w]);
+    const float p = s > -1e29f ? __expf(s - mx) : 0.0f;
+    ps[tid] = (float)(bf16)p;
+    const float sw = wave_sum(p);
+    if (lane == 0) wred[16 + wid] = sw;
+    __syncthreads();  // (also: every thread has read its red[] column sums)
+    float lsum = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) lsum += wred[16 + w];
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        const int key = kg + i * G;
+        const float pj = key < kv_total ? ps[key < 1024 ? key : 1023] : 0.0f;
+        float vv[8];
+        unpack8(vr[i], vv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
+    }
+    if (kg < G) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[kg * hd + c * 8 + e] = acc[e];
+    }
+    __syncthreads();
+    // G partial rows -> one: two levels (a single thread per output element walking all G partials is a chain of G dependent LDS reads:
+    // ~5 us of the 12 this kernel took)
+    constexpr int P2 = 1024 / hd;  // threads per output element in the first level
+    const int dd = tid % hd, j = tid / hd;
+    if (j < P2) {
+        float v = 0.0f;
+        for (int k2 = j; k2 < G; k2 += P2) v += red[k2 * hd + dd];
+        ps[j * hd + dd] = v;  // (ps is free: every p was consumed before the barrier above; P2 * hd <= 1024)
+    }
+    __syncthreads();
+    if (tid < hd) {
+        float v = 0.0f;
+#pragma unroll
+        for (int jj = 0; jj < P2; ++jj) v += ps[jj * hd + tid];
+        out[((int64_t)b * heads + h) * hd + tid] = (bf16)(lsum > 0.0f ? v / lsum : 0.0f);
+    }
+}
+
+// The same loading scheme over a RANGE of keys: 256 threads own keys [128 sp, 128 sp + 128) of one (row, head) and leave the un-normalised
+// partial (max, sum, o[hd]) in `part` — the flash-decoding format of attn_decode_split_kernel, merged by the consumer (gemv1_kernel's prologue
+// of out_proj).  One workgroup per head pulls 307 KB through ONE CU (12.1 us at batch 1); 8 splits put 38 KB on each of 256 CUs.
+// BEAM (r4, eilev_opt_decode_step_beam at <= 8 rows of head size 80): the addressing of attn_decode_split_kernel's beam form — keys below
+// seq_len in the prompt cache of sample b / beams, key seq_len + g in generation-cache row anc[g][b], the new token to this row's own slot —
+// with this kernel's 128-key ranges and up-front loads: 5 rows x 32 heads x 8 ranges = 1280 workgroups where the 256-key split kernel ran 640
+// of twice the length (15.3 us per block for 5 rows).
+template <int NCH, int VK, bool BEAM = false, int KEYS = 128>
+__global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16 *__restrict__ qkv, bf16 *__restrict__ kc, bf16 *__restrict__ vc,
+                                                               float *__restrict__ part, const int32_t *__restrict__ attn_mask,
+                                                               const int32_t *__restrict__ state, int seq_len, int cap, int heads, int64_t ldq,
+                                                               bf16 *__restrict__ kg_ = nullptr, bf16 *__restrict__ vg_ = nullptr,
+                                                               const int32_t *__restrict__ anc = nullptr, int beams = 1, int cap_g = 0, int rows = 0) {
+    constexpr int hd = NCH * 8, G = 256 / NCH, RS = NCH + 1;
+    static_assert(G * VK >= KEYS && KEYS <= 256, "every key of the range needs an owner");
+    __shared__ __attribute__((aligned(16))) float qs[128];
+    __shared__ float ps[KEYS];
+    __shared__ float wred[8];
+    __shared__ float red[KEYS * RS > G * hd ? KEYS * RS : G * hd];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y, sp = blockIdx.z, nsplit = gridDim.z, d = heads * hd;
+    const int kv_total = BEAM ? min(seq_len + cap_g, seq_len + state[0]) : min(cap, seq_len + state[0]);
+    // (beam form: a caller that passes a step count of 0, or more than the generation cache holds, must not make this row write outside its slots)
+    const int slot_new = BEAM && (kv_total - 1 < seq_len || state[0] > cap_g) ? -1 : kv_total - 1;
+    const int k0 = sp * KEYS, k1 = min(kv_total, k0 + KEYS);
+    float *po = part + (((int64_t)b * heads + h) * nsplit + sp) * (hd + 2);
+    if (k0 >= kv_total) {  // nothing in this split yet
+        if (tid == 0) {
+            po[0] = -1e30f;
+            po[1] = 0.0f;
+        }
+        return;
+    }
+    const int srow = BEAM ? b / beams : b;  // row of the prompt cache and of the attention mask
+    bf16 *kbase = kc + ((int64_t)srow * heads + h) * cap * hd, *vbase = vc + ((int64_t)srow * heads + h) * cap * hd;
+    const bf16 *knew = qkv + (int64_t)b * ldq + d + h * hd, *vnew = knew + d;
+    auto key_row = [&](const bf16 *base, const bf16 *gen, int j) -> const bf16 * {
+        if (!BEAM || j < seq_len) return base + (int64_t)j * hd;
+        const int gi = j - seq_len;
+        int a = anc[(int64_t)gi * rows + b];  // (an entry outside [0, rows) must not become an address)
+        a = a < 0 ? 0 : (a >= rows ? rows - 1 : a);
+        return gen + (((int64_t)a * heads + h) * cap_g + gi) * hd;
+    };
+    const int c = tid % NCH, kg = tid / NCH;
+    bf16x8 kr[VK], vr[VK];
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        int key = k0 + kg + i * G;
+        key = key < k1 ? key : k1 - 1;
+        kr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? knew : key_row(kbase, kg_, key)) + c * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        int key = k0 + kg + i * G;
+        key = key < k1 ? key : k1 - 1;
+        vr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? vnew : key_row(vbase, vg_, key)) + c * 8);
+    }
+    const int jt = k0 + tid;  // thread t < KEYS owns key k0 + t for the softmax
+    const bool vis = tid < KEYS && jt < k1 && (jt >= seq_len || !attn_mask || attn_mask[(int64_t)srow * seq_len + jt] != 0);
+    if (tid < hd) qs[tid] = (float)qkv[(int64_t)b * ldq + h * hd + tid];
+    if (slot_new >= k0 && slot_new < k1 && tid >= 256 - 2 * NCH) {  // the split that owns the newest slot stores it to the cache
+        const int t2 = tid - (256 - 2 * NCH), which = t2 / NCH, cc = t2 - which * NCH;
+        bf16 *dst = BEAM ? (which ? vg_ : kg_) + (((int64_t)b * heads + h) * cap_g + (slot_new - seq_len)) * hd : (which ? vbase : kbase) + (int64_t)slot_new * hd;
+        *reinterpret_cast<bf16x8 *>(dst + cc * 8) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
+    }
+    __syncthreads();
+    if (kg < G) {
+        const float4 q0 = *reinterpret_cast<const float4 *>(&qs[c * 8]), q1 = *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]);
+#pragma unroll
+        for (int i = 0; i < VK; ++i) {
+            const int kk = kg + i * G;
+            float kv[8];
+            unpack8(kr[i], kv);
+            if (kk < KEYS) red[kk * RS + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
+        }
+    }
+    __syncthreads();
+    float s = -1e30f;
+    if (tid < KEYS) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int cc = 0; cc < NCH; ++cc) acc += red[tid * RS + cc];
+        s = vis ? acc : -1e30f;
+    }
+    const float mxw = wave_max(s);
+    if (lane == 0) wred[wid] = mxw;
+    __syncthreads();
+    const float mx = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
+    const float p = s > -1e29f ? __expf(s - mx) : 0.0f;
+    if (tid < KEYS) ps[tid] = (float)(bf16)p;
+    const float sw = wave_sum(p);
+    if (lane == 0) wred[4 + wid] = sw;
+    __syncthreads();
+    const float lsum = wred[4] + wred[5] + wred[6] + wred[7];
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        const int kk = kg + i * G;
+        const float pj = (kk < KEYS && k0 + kk < k1) ? ps[kk] : 0.0f;
+        float vv[8];
+        unpack8(vr[i], vv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
+    }
+    if (kg < G) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[kg * hd + c * 8 + e] = acc[e];
+    }
+    __syncthreads();
+    if (tid < hd) {
+        float v = 0.0f;
+        for (int k2 = 0; k2 < G; ++k2) v += red[k2 * hd + tid];
+        po[2 + tid] = v;
+    }
+    if (tid == 0) {
+        po[0] = mx;
+        po[1] = lsum;
+    }
+}
+
+// ---- (round 5) any batch size: ONE workgroup per (row, head) walks the head's keys in ranges of KEYS with the loading scheme above ---------
+// At batch 32 the 128-key ranges were 8192 workgroups + a merge launch (60.7 + 6.4 us per block), 256-key ranges 4096 + 5.0 us.  Here the
+// 256 threads of a workgroup keep the flash-decoding state (max, sum, o) in registers across the ranges — the online form of the merge
+// kernel's arithmetic — and request range r + 1's keys as soon as range r's scores exist (its values after p . V): no partials, no merge
+// launch, the normalised row straight to `out`.  32 rows x 32 heads = 1024 workgroups = 4 per CU, all resident at once.
+// (measured and not kept: 128-key ranges at 4 workgroups per CU, 4.33 against 4.28 ms / token; 256-key ranges forced to 128 registers spill)
+template <int NCH, int VK, int KEYS>
+__global__ __launch_bounds__(256) void attn_decode_loop_kernel(const bf16 *__restrict__ qkv, bf16 *__restrict__ kc, bf16 *__restrict__ vc,
+                                                               bf16 *__restrict__ out, const int32_t *__restrict__ attn_mask,
+                                                               const int32_t *__restrict__ state, int seq_len, int cap, int heads, int64_t ldq,
+                                                               int out_frag, int fuse_new, const float *__restrict__ rel_tab = nullptr,
+                                                               int64_t rel_hs = 0, int rel_off = 0) {
+    // state == nullptr: kv_total = seq_len, given by the host (the flan-t5 cross-attention: keys = encoder positions, attn_mask = their
+    // padding mask, q rows of stride ldq); fuse_new == 0: every key is in the cache already
+    constexpr int hd = NCH * 8, G = 256 / NCH, RS = NCH + 1;
+    static_assert(G * VK >= KEYS && KEYS <= 256, "every key of a range needs an owner");
+    __shared__ __attribute__((aligned(16))) float qs[128];
+    __shared__ float ps[KEYS];
+    __shared__ float wred[8];
+    __shared__ float red[KEYS * RS > G * hd ? KEYS * RS : G * hd];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y, d = heads * hd;
+    const int kv_total = min(cap, seq_len + (state ? state[0] : 0));
+    const int slot_new = fuse_new ? kv_total - 1 : -1;
+    bf16 *kbase = kc + ((int64_t)b * heads + h) * cap * hd, *vbase = vc + ((int64_t)b * heads + h) * cap * hd;
+    const bf16 *knew = qkv + (int64_t)b * ldq + d + h * hd, *vnew = knew + d;
+    const int c = tid % NCH, kg = tid / NCH;
+    bf16x8 kr[VK], vr[VK];
+    auto load_k = [&](int k0) {
+        const int k1 = min(kv_total, k0 + KEYS);
+#pragma unroll
+        for (int i = 0; i < VK; ++i) {
+            int key = k0 + kg + i * G;
+            key = key < k1 ? key : k1 - 1;
+            kr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? knew : kbase + (int64_t)key * hd) + c * 8);
+        }
+    };
+    auto load_v = [&](int k0) {
+        const int k1 = min(kv_total, k0 + KEYS);
+#pragma unroll
+        for (int i = 0; i < VK; ++i) {
+            int key = k0 + kg + i * G;
+            key = key < k1 ? key : k1 - 1;
+            vr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? vnew : vbase + (int64_t)key * hd) + c * 8);
+        }
+    };
+    load_k(0);
+    load_v(0);
+    if (tid < hd) qs[tid] = (float)qkv[(int64_t)b * ldq + h * hd + tid];
+    if (fuse_new && tid >= 256 - 2 * NCH) {  // the newest key / value: from the q|k|v row of this step into the cache (fuse_new of the split kernel)
+        const int t2 = tid - (256 - 2 * NCH), which = t2 / NCH, cc = t2 - which * NCH;
+        bf16 *dst = (which ? vbase : kbase) + (int64_t)slot_new * hd;
+        *reinterpret_cast<bf16x8 *>(dst + cc * 8) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
+    }
+    __syncthreads();
+    const float4 q0 = *reinterpret_cast<const float4 *>(&qs[c * 8]), q1 = *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]);
+    float m_run = -1e30f, l_run = 0.0f;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+    for (int k0 = 0; k0 < kv_total; k0 += KEYS) {
+        const int k1 = min(kv_total, k0 + KEYS);
+        if (kg < G) {
+#pragma unroll
+            for (int i = 0; i < VK; ++i) {
+                const int kk = kg + i * G;
+                float kv[8];
+                unpack8(kr[i], kv);
+                if (kk < KEYS) red[kk * RS + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
+            }
+        }
+        if (k0 + KEYS < kv_total) load_k(k0 + KEYS);  // (uniform) the next range's keys: in flight under this range's softmax and p . V
+        __syncthreads();
+        const int jt = k0 + tid;
+        float s = -1e30f;
+        if (tid < KEYS && jt < k1 && (jt >= seq_len || !attn_mask || attn_mask[(int64_t)b * seq_len + jt] != 0)) {
+            float a = 0.0f;
+#pragma unroll
+            for (int cc = 0; cc < NCH; ++cc) a += red[tid * RS + cc];
+            // (flan-t5 self-attention: per-head position bias over key - query position, the query at kv_total - 1; rel_off < 0: the table of this query row)
+            if (rel_tab) a += rel_tab[(int64_t)h * rel_hs + (rel_off >= 0 ? (jt - (kv_total - 1)) + rel_off : jt)];
+            s = a;
+        }
+        const float mxw = wave_max(s);
+        if (lane == 0) wred[wid] = mxw;
+        __syncthreads();
+        const float m_new = fmaxf(m_run, fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3])));
+        const float p = s > -1e29f ? __expf(s - m_new) : 0.0f;
+        if (tid < KEYS) ps[tid] = (float)(bf16)p;  // P rounded to bf16 for the product like every attention kernel here; the row sum from the unrounded values
+        const float sw = wave_sum(p);
+        if (lane == 0) wred[4 + wid] = sw;
+        __syncthreads();
+        const float scale = __expf(m_run - m_new);  // first range: exp(-huge) = 0 (and the state it scales is 0)
+        l_run = l_run * scale + (wred[4] + wred[5] + wred[6] + wred[7]);
+        m_run = m_new;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] *= scale;
+#pragma unroll
+        for (int i = 0; i < VK; ++i) {
+            const int kk = kg + i * G;
+            const float pj = (kk < KEYS && k0 + kk < k1) ? ps[kk] : 0.0f;
+            float vv[8];
+            unpack8(vr[i], vv);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
+        }
+        if (k0 + KEYS < kv_total) load_v(k0 + KEYS);
+        __syncthreads();  // ps / red / wred are rewritten by the next range
+    }
+    if (kg < G) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[kg * hd + c * 8 + e] = acc[e];
+    }
+    __syncthreads();
+    if (tid < hd) {
+        float v = 0.0f;
+        for (int k2 = 0; k2 < G; ++k2) v += red[k2 * hd + tid];
+        // out_frag: the row-block layout out_proj's GEMV reads at 17..32 rows (common.h frag32_index)
+        out[out_frag ? frag32_index(b, h * hd + tid) : ((int64_t)b * heads + h) * hd + tid] = (bf16)(l_run > 0.0f ? v / l_run : 0.0f);
+    }
+}
+
+__global__ __launch_bounds__(128) void attn_decode_merge_kernel(const float *__restrict__ part, bf16 *__restrict__ out,
+                                                                int heads, int hd, int nsplit) {
+    const int h = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const float *pp = part + ((int64_t)b * heads + h) * nsplit * (hd + 2);
+    float mx = -1e30f;
+    for (int s = 0; s < nsplit; ++s) mx = fmaxf(mx, pp[s * (hd + 2)]);
+    float l = 0.0f, o = 0.0f;
+    for (int s = 0; s < nsplit; ++s) {
+        const float *ps = pp + s * (hd + 2);
+        const float w = ps[1] > 0.0f ? __expf(ps[0] - mx) : 0.0f;
+        l += w * ps[1];
+        if (t < hd && w > 0.0f) o += w * ps[2 + t];
+    }
+    if (t < hd) out[((int64_t)b * heads + h) * hd + t] = (bf16)(l > 0.0f ? o / l : 0.0f);
+}
+
+}  // namespace
+
+static int g_beam_part = 1;
+static int g_attn_part32 = 1;  // 1 = by batch size (launch_attn_decode); probe build: 0 = the 256-key split kernel, 2 / 3 = force a form
+#ifdef EILEV_PROBES
+extern "C" int eilev_debug_attn_part32(int on) { g_attn_part32 = on; return 0; }  // probe: the 128-key up-front-load kernel at any batch size
+extern "C" int eilev_debug_beam_part(int on) { g_beam_part = on; return 0; }  // probe / test switch: 0 = the 256-key split kernel for beam rows too (round 3)
+#endif
+size_t attn_decode_part_bytes(int batch, int heads, int hd, int keys, int range) {
+    return sizeof(float) * (size_t)batch * heads * ceil_div64(keys, range) * (hd + 2);
+}
+// the launch takes attn_decode_loop_kernel (one workgroup per (row, head), no partials): the only form that can write the row-block layout
+bool attn_decode_loop_ok(const DecodeAttnArgs &a) {
+    return g_attn_part32 == 1 && !a.anc && a.out && a.state && a.fuse_new && !a.rel_tab && a.hd == 80 && a.keys() <= 2048 &&
+           a.batch * a.heads >= 2 * eilev_num_cu() && a.batch <= 32;
+}
+int launch_attn_decode(const DecodeAttnArgs &a, hipStream_t s, int *nsplit) {
+    if (!a.out && !nsplit) return EILEV_E_BADARG;  // partials are left only to a caller that merges them
+    if (a.out_frag && !attn_decode_loop_ok(a)) return EILEV_E_UNSUPPORTED;
+    const int batch = a.batch, heads = a.heads, hd = a.hd, cap_all = a.keys();  // beam form: prompt keys (prefill cache) + generated keys (generation cache)
+    if (hd > 128 || (hd & 7)) return EILEV_E_UNSUPPORTED;
+    const int64_t ldq = a.q_stride();
+    bf16 *kc = const_cast<bf16 *>(a.kc), *vc = const_cast<bf16 *>(a.vc);
+    auto fits = [&](int range) { return a.part && a.part_bytes >= attn_decode_part_bytes(batch, heads, hd, cap_all, range); };
+    auto merge = [&](int ns) {
+        hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(heads, batch), dim3(128), 0, s, a.part, a.out, heads, hd, ns);
+        EILEV_LAUNCH_CHECK();
+        return EILEV_OK;
+    };
+    if (a.anc && a.out && a.state && a.fuse_new && !a.rel_tab && hd == 80 && batch <= 8 && cap_all <= 2048 && g_beam_part) {
+        // (r4) beam search at <= 8 rows: 128-key ranges with up-front loads (attn_decode_part_kernel<.., BEAM>), then the same merge
+        const int ns = (int)ceil_div64(cap_all, 128);
+        if (fits(128)) {
+            hipLaunchKernelGGL((attn_decode_part_kernel<10, 6, true>), dim3(heads, batch, ns), dim3(256), 0, s, a.qkv, kc, vc, a.part, a.attn_mask, a.state,
+                               a.seq_len, a.cap, heads, ldq, a.kg, a.vg, a.anc, a.beams, a.cap_g, batch);
+            EILEV_LAUNCH_CHECK();
+            return merge(ns);
+        }
+    }
+    // (r5) hd 64 (flan-t5: the cross-attention over 960 encoder keys — state == nullptr, nothing to store — and the self-attention with its position bias): the per-head loop too
+    if (g_attn_part32 == 1 && !a.anc && a.out && hd == 64 && batch * heads >= 2 * eilev_num_cu()) {
+        hipLaunchKernelGGL((attn_decode_loop_kernel<8, 8, 256>), dim3(heads, batch), dim3(256), 0, s, a.qkv, kc, vc, a.out, a.attn_mask, a.state, a.seq_len,
+                           a.cap, heads, ldq, 0, a.fuse_new, a.rel_tab, a.rel_hs, a.rel_off);
+        EILEV_LAUNCH_CHECK();
+        return EILEV_OK;
+    }
+    if (g_attn_part32 && !a.anc && a.out && a.state && a.fuse_new && !a.rel_tab && hd == 80 && cap_all <= 2048) {
+        // (r5) plain decode steps of head size 80 at any batch size, same-box ms / token at batch 32: 256-key split kernel + merge 4.70,
+        // 128-key up-front-load ranges + merge 4.61 (mode 1), 256-key ranges 4.38 (mode 2), one workgroup per head looping over 256-key
+        // ranges with no partials and no merge 4.27 (mode 3, the default from 2 workgroups per CU; fewer rows keep the ranges: more workgroups)
+        const int mode = g_attn_part32 != 1 ? g_attn_part32 : (batch * heads >= 2 * eilev_num_cu() ? 3 : 1);
+        if (mode == 3) {
+            hipLaunchKernelGGL((attn_decode_loop_kernel<10, 11, 256>), dim3(heads, batch), dim3(256), 0, s, a.qkv, kc, vc, a.out, a.attn_mask, a.state,
+                               a.seq_len, a.cap, heads, ldq, a.out_frag, 1);
+            EILEV_LAUNCH_CHECK();
+            return EILEV_OK;
+        }
+        const int keys = mode == 2 ? 256 : 128;
+        const int ns = (int)ceil_div64(cap_all, keys);
+        if (fits(keys)) {
+            if (keys == 256)
+                hipLaunchKernelGGL((attn_decode_part_kernel<10, 11, false, 256>), dim3(heads, batch, ns), dim3(256), 0, s, a.qkv, kc, vc, a.part, a.attn_mask,
+                                   a.state, a.seq_len, a.cap, heads, ldq, nullptr, nullptr, nullptr, 1, 0, batch);
+            else
+                hipLaunchKernelGGL((attn_decode_part_kernel<10, 6, false>), dim3(heads, batch, ns), dim3(256), 0, s, a.qkv, kc, vc, a.part, a.attn_mask,
+                                   a.state, a.seq_len, a.cap, heads, ldq, nullptr, nullptr, nullptr, 1, 0, batch);
+            EILEV_LAUNCH_CHECK();
+            return merge(ns);
+        }
+    }
+    const int ns = (int)ceil_div64(cap_all, DEC_KEYS);
+    if (!fits(DEC_KEYS)) return EILEV_E_WORKSPACE;
+    hipLaunchKernelGGL(attn_decode_split_kernel, dim3(heads, batch, ns), dim3(256), 0, s, a.qkv, a.kc, a.vc, a.part, a.attn_mask, a.state, a.seq_len, a.cap,
+                       heads, hd, ldq, a.rel_tab, a.rel_hs, a.rel_off, a.fuse_new, a.kg, a.vg, a.anc, a.beams, a.cap_g, batch);
+    EILEV_LAUNCH_CHECK();
+    if (!a.out) {  // the caller merges the partials itself (gemv.hip: in the prologue of out_proj)
+        *nsplit = ns;
+        return EILEV_OK;
+    }
+    return merge(ns);
+}
+// plain decode step at small batch (no beams, no relative bias): true if the one-pass kernel took it
+bool attn_decode1_ok(int batch, int cap, int hd) {
+    if (batch > 8 || cap > 1024) return false;
+    if (hd == 80) return cap <= 12 * (1024 / 10);
+    if (hd == 64) return cap <= 8 * (1024 / 8);
+    return false;  // (head size 128: 74 KB of static LDS for the partials — the split kernel)
+}
+int launch_attn_decode1(const DecodeAttnArgs &a, hipStream_t s) {
+    if (!attn_decode1_ok(a.batch, a.cap, a.hd) || !a.state || !a.out) return EILEV_E_UNSUPPORTED;
+    bf16 *kc = const_cast<bf16 *>(a.kc), *vc = const_cast<bf16 *>(a.vc);
+    const dim3 grid(a.heads, a.batch);
+    if (a.hd == 80) hipLaunchKernelGGL((attn_decode1_kernel<10, 12>), grid, dim3(1024), 0, s, a.qkv, kc, vc, a.out, a.attn_mask, a.state, a.seq_len, a.cap, a.heads, a.q_stride());
+    else hipLaunchKernelGGL((attn_decode1_kernel<8, 8>), grid, dim3(1024), 0, s, a.qkv, kc, vc, a.out, a.attn_mask, a.state, a.seq_len, a.cap, a.heads, a.q_stride());
+    EILEV_LAUNCH_CHECK();
+    return EILEV_OK;
+}
+int launch_attn_decode_part(const DecodeAttnArgs &a, hipStream_t s, int *nsplit) {
+    if (a.hd != 80 || a.cap > 1024 || !a.state || !a.part) return EILEV_E_UNSUPPORTED;
+    if (a.part_bytes < attn_decode_part_bytes(a.batch, a.heads, a.hd, a.cap)) return EILEV_E_WORKSPACE;
+    const int ns = (int)ceil_div64(a.cap, 128);
+    hipLaunchKernelGGL((attn_decode_part_kernel<10, 6>), dim3(a.heads, a.batch, ns), dim3(256), 0, s, a.qkv, const_cast<bf16 *>(a.kc), const_cast<bf16 *>(a.vc),
+                       a.part, a.attn_mask, a.state, a.seq_len, a.cap, a.heads, a.q_stride());
+    EILEV_LAUNCH_CHECK();
+    *nsplit = ns;
+    return EILEV_OK;
+}

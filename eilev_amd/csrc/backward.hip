@@ -811,7 +811,6 @@ extern "C" int eilev_ce_loss(const float *logits, const int64_t *targets, float 
 }
 
 // ---- encoder-decoder (T5) language model: forward building blocks the training graph composes, and their gradients ----------------
-int launch_gated_gelu(const bf16 *ab, int64_t ld, bf16 *out, int64_t rows, int F, hipStream_t s);
 
 extern "C" int eilev_attention_dropout(const void *q, const void *k, const void *v, void *o, int64_t batch, int64_t heads, int64_t sq,
                                        int64_t skv, int64_t head_dim, int64_t ldq, int64_t ldk, int64_t ldv, float scale, int causal,

@@ -357,6 +357,7 @@ struct GemmArgs {
 __host__ __device__ static inline int64_t frag32_index(int row, int col) { return (int64_t)(col >> 5) * 1024 + row * 32 + (col & 31); }
 
 int launch_gemm(const GemmArgs &g, int prof_kind, hipStream_t s);
+bool gemm_rows32_takes(const GemmArgs &g);  // would launch_gemm run g on gemm_rows32_kernel (the one kernel of the row-block layout)?
 int launch_pp4_ext(const GemmArgs &g, int grid, hipStream_t s);  // gemm_pp4_ext.hip
 // every tile of a persistent-kernel launch can take the lean epilogue (what the 16 x 16 MFMA instances need: gemm_pp4.h M16)
 // Probe build: the per-tile stamps of tools/gemm_trace.py / gemm_timeline.py run on the product's 16 x 16 instances.  (In rounds 2-5 a trace
@@ -391,18 +392,32 @@ int launch_gemv1(int pro, const bf16 *x, const bf16 *gamma, const bf16 *beta, fl
 bool gemvm_ok(int M, int N, int K, int pro);  // 2 <= M <= 8 rows with the same geometry, rows staged in LDS (round 4)
 int launch_gemvm(int pro, const bf16 *x, int64_t ldx, const bf16 *gamma, const bf16 *beta, float eps, const bf16 *W, const bf16 *bias, const bf16 *resid,
                  int64_t ldr, void *out, int64_t ldo, int out_f32, int M, int N, int K, int epi, float scale, int scale_cols, hipStream_t s);
-// misc.hip: single-query attention at small batch, one workgroup per (row, head), merged output (round 4)
-bool attn_decode1_ok(int batch, int cap, int hd);
+// misc.hip: the glue kernels
+int launch_im2col(const void *pix, int dtype, bf16 *out, int64_t rows, int frames, int img, int patch, int kp, hipStream_t s);
+int launch_pad_rows(const bf16 *w, bf16 *out, int rows, int k, int kp, hipStream_t s);
+int launch_cls_rows(const bf16 *cls, const bf16 *pos, bf16 *x, int64_t frames_total, int tok, int d, hipStream_t s);
+int launch_quant_rows_e4m3(const bf16 *x, int64_t ldx, uint8_t *q, float *scale, int64_t rows, int cols, hipStream_t s);
+int launch_broadcast_rows(const bf16 *src, bf16 *dst, int64_t copies, int64_t n, hipStream_t s);
+int launch_embed_scatter(const bf16 *embed, const int64_t *ids, const uint8_t *mask, const bf16 *feats, int64_t n_rows,
+                         int64_t total, int vocab, bf16 *out, int d, hipStream_t s);
+int launch_pos_embed(const bf16 *emb, const bf16 *pos, const int32_t *mask, int32_t *pid, bf16 *h, int batch, int L, int d, hipStream_t s,
+                     int past = 0);
+int launch_decode_embed(const bf16 *embed, const bf16 *pos, const int64_t *tokens, const int32_t *n_valid, const int32_t *state,
+                        int vocab, int max_pid, bf16 *h, int batch, int d, hipStream_t s);
+int launch_kv_write(const bf16 *qkv, bf16 *kc, bf16 *vc, int batch, int rows_per_b, int heads, int hd, int cap, int seq_len,
+                    const int32_t *state, hipStream_t s, int slot0 = 0);
+int launch_select(const float *logits, int batch, int vocab, int32_t *state, uint8_t *finished, int64_t eos_id, int64_t pad_id,
+                  int64_t *tokens, int64_t *out_tokens, int64_t max_new, hipStream_t s);
+int launch_topk_logprob(const float *logits, const float *row_score, int rows, int vocab, int keep, float *out_val, int32_t *out_idx, hipStream_t s);
 int launch_beam_advance(const float *row_lp, const int32_t *row_tok, int batch, int beams, int keep, int max_new, const int32_t *state,
                         const int64_t *eos_ids, int n_eos, const float *len_pow, int recip, int early, int64_t *run_seq, float *run_score,
                         int64_t *fin_seq, float *fin_score, int64_t *fin_len, uint8_t *finished, uint8_t *can_improve, int64_t *tokens, int32_t *anc,
                         int gen_cap, int64_t *scratch, hipStream_t s);
-int launch_topk_logprob(const float *logits, const float *row_score, int rows, int vocab, int keep, float *out_val, int32_t *out_idx, hipStream_t s);
-int launch_attn_decode1(const bf16 *qkv, bf16 *kc, bf16 *vc, bf16 *out, const int32_t *attn_mask, const int32_t *state, int batch, int seq_len,
-                        int cap, int heads, int hd, hipStream_t s);
-int attn_decode_part_splits(int cap);  // misc.hip: the one-pass loading scheme over 128-key ranges, partials for gemv1_kernel's merge prologue (round 4)
-int launch_attn_decode_part(const bf16 *qkv, bf16 *kc, bf16 *vc, float *part, size_t part_bytes, const int32_t *attn_mask, const int32_t *state, int batch,
-                            int seq_len, int cap, int heads, int hd, hipStream_t s);
+int launch_t5_rel_table(const bf16 *rel_w, float *tab, int n, int off, int heads, int bidirectional, int num_buckets, int max_dist,
+                        hipStream_t s, const int32_t *state = nullptr);
+int launch_gated_gelu(const bf16 *ab, int64_t ld, bf16 *out, int64_t rows, int F, hipStream_t s);
+int launch_rows_to_cache(const bf16 *src, int64_t ld, int col0, bf16 *plane, int batch, int rows_per_b, int heads, int hd, int cap,
+                         int slot0, hipStream_t s, const int32_t *state = nullptr);
 int launch_layernorm(const bf16 *x, int64_t ldx, const bf16 *g, const bf16 *b, bf16 *y, int64_t ldy, int64_t rows,
                      int cols, float eps, hipStream_t s);
 int launch_fold_layernorm(const bf16 *w, const bf16 *gamma, const bf16 *beta, const bf16 *bias, int N, int K, bf16 *wf, float *csum, bf16 *bf,
@@ -437,6 +452,42 @@ struct AttnArgs {
     float drop_scale = 1.0f;
 };
 int launch_attention(const AttnArgs &a, hipStream_t s);
+
+// attn_decode.hip: the single query of a decode step per (row, head) against a KV cache.  Host side only: the launchers choose a kernel and
+// pass these values on as its arguments.
+struct DecodeAttnArgs {
+    const bf16 *qkv = nullptr;        // query rows, row stride ldq; with fuse_new q | k | v of the step (the new token's K / V follow q)
+    int64_t ldq = 0;                  // 0: 3 * heads * hd (q | k | v rows)
+    const bf16 *kc = nullptr, *vc = nullptr;  // cache planes [batch][heads][cap][hd] (beam form: the prompt cache, one row per sample)
+    bf16 *out = nullptr;              // [batch][heads * hd]; null: launch_attn_decode leaves the partials of the 256-key split kernel in `part`
+    const int32_t *attn_mask = nullptr;  // (batch, seq_len) or null: keys < seq_len obey it, newer ones are visible
+    const int32_t *state = nullptr;   // kv_total = seq_len + state[0], read on the device (hipGraph replay); null: kv_total = seq_len
+    int batch = 0, seq_len = 0, cap = 0, heads = 0, hd = 0;
+    float *part = nullptr; size_t part_bytes = 0;  // flash-decoding partials: (max, sum, o[hd]) floats per (row, head, key range)
+    int fuse_new = 0;                 // the newest key / value is still only in the q|k|v row: the kernel stores it into the cache
+    // T5 position bias rel_tab[h * rel_hs + (key - query) + rel_off], the query at kv_total - 1 (rel_off < 0: this query row's table, entry j = key j)
+    const float *rel_tab = nullptr;
+    int64_t rel_hs = 0; int rel_off = 0;
+    // beam search without moving the cache: row b is beam b % beams of sample b / beams; key seq_len + g is the g-th generated token of its
+    // hypothesis, in row anc[g * batch + b] of the generation cache kg / vg (capacity cap_g); the new token goes to the row's own slot
+    bf16 *kg = nullptr, *vg = nullptr;
+    const int32_t *anc = nullptr;
+    int beams = 1, cap_g = 0;
+    int out_frag = 0;                 // `out` in the row-block layout (frag32_index): attn_decode_loop_kernel only (attn_decode_loop_ok)
+    int64_t q_stride() const { return ldq ? ldq : 3 * (int64_t)heads * hd; }
+    int keys() const { return anc ? seq_len + cap_g : cap; }  // the cache slots a row can attend to
+};
+// partials of `keys` keys in ranges of `range` keys; the 128-key ranges (the default) need the most of any form
+size_t attn_decode_part_bytes(int batch, int heads, int hd, int keys, int range = 128);
+bool attn_decode_loop_ok(const DecodeAttnArgs &a);  // the launch takes attn_decode_loop_kernel: the only form that writes the row-block layout
+// The merged rows into a.out, the kernel chosen by batch size, head size and flags.  a.out == nullptr: the partials of the 256-key split
+// kernel stay in a.part for the caller to merge (gemv_rows_kernel's prologue), *nsplit = their ranges per (row, head).
+int launch_attn_decode(const DecodeAttnArgs &a, hipStream_t s, int *nsplit = nullptr);
+// plain steps at small batch (state, fuse_new; no beams, no bias): one workgroup per (row, head), every key in one pass (round 4)
+bool attn_decode1_ok(int batch, int cap, int hd);
+int launch_attn_decode1(const DecodeAttnArgs &a, hipStream_t s);
+// ... the same loading scheme over 128-key ranges, partials for gemv1_kernel's merge prologue; *nsplit = the ranges per (row, head)
+int launch_attn_decode_part(const DecodeAttnArgs &a, hipStream_t s, int *nsplit);
 int launch_rmsnorm(const bf16 *x, int64_t ldx, const bf16 *g, bf16 *y, int64_t ldy, int64_t rows, int cols, float eps, hipStream_t s);
 
 void prof_begin(int kind, double flops, hipStream_t s);

@@ -6,35 +6,6 @@
 
 #include "common.h"
 
-int launch_im2col(const void *pix, int dtype, bf16 *out, int64_t rows, int frames, int img, int patch, int kp, hipStream_t s);
-int launch_pad_rows(const bf16 *w, bf16 *out, int rows, int k, int kp, hipStream_t s);
-int launch_cls_rows(const bf16 *cls, const bf16 *pos, bf16 *x, int64_t frames_total, int tok, int d, hipStream_t s);
-int launch_quant_rows_e4m3(const bf16 *x, int64_t ldx, uint8_t *q, float *scale, int64_t rows, int cols, hipStream_t s);
-int launch_broadcast_rows(const bf16 *src, bf16 *dst, int64_t copies, int64_t n, hipStream_t s);
-int launch_embed_scatter(const bf16 *embed, const int64_t *ids, const uint8_t *mask, const bf16 *feats, int64_t n_rows,
-                         int64_t total, int vocab, bf16 *out, int d, hipStream_t s);
-int launch_pos_embed(const bf16 *emb, const bf16 *pos, const int32_t *mask, int32_t *pid, bf16 *h, int batch, int L, int d, hipStream_t s,
-                     int past = 0);
-int launch_decode_embed(const bf16 *embed, const bf16 *pos, const int64_t *tokens, const int32_t *n_valid, const int32_t *state,
-                        int vocab, int max_pid, bf16 *h, int batch, int d, hipStream_t s);
-int launch_kv_write(const bf16 *qkv, bf16 *kc, bf16 *vc, int batch, int rows_per_b, int heads, int hd, int cap, int seq_len,
-                    const int32_t *state, hipStream_t s, int slot0 = 0);
-int launch_attn_decode(const bf16 *qkv, const bf16 *kc, const bf16 *vc, bf16 *out, const int32_t *attn_mask, const int32_t *state,
-                       int batch, int seq_len, int cap, int heads, int hd, float *scratch, size_t scratch_bytes, hipStream_t s,
-                       int64_t ldq = 0, const float *rel_tab = nullptr, int64_t rel_hs = 0, int rel_off = 0, int fuse_new = 0,
-                       const bf16 *kg = nullptr, const bf16 *vg = nullptr, const int32_t *anc = nullptr, int beams = 1, int cap_g = 0, int out_frag = 0);
-bool attn_decode_loop_ok(int batch, int heads, int hd, int cap_all, bool beam, const void *out, const void *state, int fuse_new, const void *rel_tab);
-bool gemm_rows32_takes(const GemmArgs &g);  // gemm.hip
-size_t attn_decode_scratch_bytes(int batch, int heads, int hd, int cap);
-int launch_select(const float *logits, int batch, int vocab, int32_t *state, uint8_t *finished, int64_t eos_id, int64_t pad_id,
-                  int64_t *tokens, int64_t *out_tokens, int64_t max_new, hipStream_t s);
-
-int launch_t5_rel_table(const bf16 *rel_w, float *tab, int n, int off, int heads, int bidirectional, int num_buckets, int max_dist,
-                        hipStream_t s, const int32_t *state = nullptr);
-int launch_gated_gelu(const bf16 *ab, int64_t ld, bf16 *out, int64_t rows, int F, hipStream_t s);
-int launch_rows_to_cache(const bf16 *src, int64_t ld, int col0, bf16 *plane, int batch, int rows_per_b, int heads, int hd, int cap,
-                         int slot0, hipStream_t s, const int32_t *state = nullptr);
-
 #define RC(expr)                 \
     do {                         \
         int _rc = (expr);        \
@@ -604,19 +575,14 @@ int opt_tail(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs 
     return launch_gemm(g, 5, s);
 }
 
-// ---- small-batch decode (M <= 8 rows): the block as 5 launches of gemv.hip + the attention split ---------------------------------------
+// ---- small-batch decode (M <= 4 rows): the block as 5 launches of gemv.hip + the attention -------------------------------------------
 int g_decode_frag = 1;  // probe / test switch (eilev_debug_decode_frag, probe build): 0 = row-major activations in the 17..32-row decode step
 int g_decode_rows = 1;  // probe / test switch (eilev_debug_decode_rows): 0 = the MFMA weight-streaming kernels at every batch size
-constexpr int kDecodeKeys = 256;  // keys per flash-decoding split (misc.hip DEC_KEYS)
 
-// Measured (tools/beam_probe.py, OPT-2.7B, L = 960, ms per token under hipGraph): rows 1: 2.27 against 2.64 for the MFMA weight-streaming
-// kernels, 2: 2.67 (~2.7), 3: 2.89 (~2.8), 5: 4.07 against 2.87 — every extra row costs the dot-product kernel a pass of LDS reads and
-// v_dot2c per weight chunk, the MFMA kernels nothing up to 16 rows.  So: M <= 2 (latency mode; one sample per GPU of a strong-scaled step).
-bool opt_rows_usable(const EilevDims *d, const EilevOptWeights *w, int64_t M) {
-    if (!g_decode_rows || w->layers_w8 || M > 2) return false;
+// q | k | v of every block must be ONE [3 D, D] matrix with one bias vector (the engine packs them so)
+bool opt_qkv_packed(const EilevDims *d, const EilevOptWeights *w) {
     const int D = d->t_hidden;
-    if (!gemv_rows_ok((int)M, D, D) || !gemv_rows_ok((int)M, D, d->t_ffn) || (D / d->t_heads) % 8) return false;
-    for (int l = 0; l < d->t_layers; ++l) {  // q | k | v must be ONE [3 D, D] matrix with one bias vector (the engine packs them so)
+    for (int l = 0; l < d->t_layers; ++l) {
         const EilevOptLayer *L = &w->layers[l];
         const bf16 *qw = (const bf16 *)L->q_w, *qb = (const bf16 *)L->q_b;
         if ((const bf16 *)L->k_w != qw + (size_t)D * D || (const bf16 *)L->v_w != qw + 2 * (size_t)D * D || !qb || (const bf16 *)L->k_b != qb + D ||
@@ -624,6 +590,14 @@ bool opt_rows_usable(const EilevDims *d, const EilevOptWeights *w, int64_t M) {
             return false;
     }
     return true;
+}
+// Measured (tools/beam_probe.py, OPT-2.7B, L = 960, ms per token under hipGraph): rows 1: 2.27 against 2.64 for the MFMA weight-streaming
+// kernels, 2: 2.67 (~2.7), 3: 2.89 (~2.8), 5: 4.07 against 2.87 — every extra row costs the dot-product kernel a pass of LDS reads and
+// v_dot2c per weight chunk, the MFMA kernels nothing up to 16 rows.  So: M <= 2 (latency mode; one sample per GPU of a strong-scaled step).
+bool opt_rows_usable(const EilevDims *d, const EilevOptWeights *w, int64_t M) {
+    if (!g_decode_rows || w->layers_w8 || M > 2) return false;
+    const int D = d->t_hidden;
+    return gemv_rows_ok((int)M, D, D) && gemv_rows_ok((int)M, D, d->t_ffn) && (D / d->t_heads) % 8 == 0 && opt_qkv_packed(d, w);
 }
 // batch 1 (latency mode; one sample per GPU of a strong-scaled step): gemv1_kernel + attn_decode1_kernel.  eilev_debug_decode_rows(3) = off
 bool opt_rows1_usable(const EilevDims *d, const EilevOptWeights *w, int64_t M, int64_t cap) {
@@ -638,15 +612,7 @@ bool opt_rowsm_usable(const EilevDims *d, const EilevOptWeights *w, int64_t M) {
     // weight-streaming kernels, whose cost is flat up to 16 rows: every extra row costs this kernel a pass of LDS reads + dot products
     if (M < 2 || M > 4 || g_decode_rows == 3 || !g_decode_rows || w->layers_w8) return false;
     const int D = d->t_hidden;
-    if (!gemvm_ok((int)M, 3 * D, D, 1) || !gemvm_ok((int)M, D, D, 0) || (D / d->t_heads) % 8 || (d->vocab & 1)) return false;
-    for (int l = 0; l < d->t_layers; ++l) {  // q | k | v must be ONE [3 D, D] matrix with one bias vector (the engine packs them so)
-        const EilevOptLayer *L = &w->layers[l];
-        const bf16 *qw = (const bf16 *)L->q_w, *qb = (const bf16 *)L->q_b;
-        if ((const bf16 *)L->k_w != qw + (size_t)D * D || (const bf16 *)L->v_w != qw + 2 * (size_t)D * D || !qb || (const bf16 *)L->k_b != qb + D ||
-            (const bf16 *)L->v_b != qb + 2 * D)
-            return false;
-    }
-    return true;
+    return gemvm_ok((int)M, 3 * D, D, 1) && gemvm_ok((int)M, D, D, 0) && (D / d->t_heads) % 8 == 0 && !(d->vocab & 1) && opt_qkv_packed(d, w);
 }
 // block l without its attention: LayerNorm + q|k|v (before), out_proj + residual, LayerNorm + fc1 + ReLU, fc2 + residual (after)
 int opt_rowsm_qkv(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s) {
@@ -680,15 +646,13 @@ int opt_rows_qkv(const EilevDims *d, const EilevOptWeights *w, int l, const OptB
     return launch_gemv_rows(1, b.h, D, (const bf16 *)L->ln1_w, (const bf16 *)L->ln1_b, d->t_eps, nullptr, 0, 0, 0, (const bf16 *)L->q_w, (const bf16 *)L->q_b,
                             nullptr, 0, b.qkv, 3 * D, 0, (int)M, 3 * D, D, 0, 1.0f / sqrtf((float)(D / d->t_heads)), D, s);
 }
-// (merge +) out_proj + residual, final_layer_norm + fc1 + ReLU, fc2 + residual: b.h -> b.h.  part != nullptr: the attention partials are
-// merged in the prologue of out_proj (M <= 2: every workgroup repeats the merge); otherwise b.att holds the merged rows.
+// merge + out_proj + residual, final_layer_norm + fc1 + ReLU, fc2 + residual: b.h -> b.h.  The attention's flash-decoding partials (nsplit
+// ranges per row and head) are merged in the prologue of out_proj (every workgroup repeats the merge: M <= 2).
 int opt_rows_tail(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, const float *part, int nsplit, hipStream_t s) {
     const EilevOptLayer *L = &w->layers[l];
     const int D = d->t_hidden, Ft = d->t_ffn, H = d->t_heads;
-    if (part) RC(launch_gemv_rows(2, nullptr, 0, nullptr, nullptr, 0.f, part, H, D / H, nsplit, (const bf16 *)L->o_w, (const bf16 *)L->o_b, b.h, D, b.h, D, 0,
-                                  (int)M, D, D, 0, 1.0f, 0, s));
-    else RC(launch_gemv_rows(0, b.att, D, nullptr, nullptr, 0.f, nullptr, 0, 0, 0, (const bf16 *)L->o_w, (const bf16 *)L->o_b, b.h, D, b.h, D, 0, (int)M, D, D, 0,
-                             1.0f, 0, s));
+    RC(launch_gemv_rows(2, nullptr, 0, nullptr, nullptr, 0.f, part, H, D / H, nsplit, (const bf16 *)L->o_w, (const bf16 *)L->o_b, b.h, D, b.h, D, 0,
+                        (int)M, D, D, 0, 1.0f, 0, s));
     RC(launch_gemv_rows(1, b.h, D, (const bf16 *)L->ln2_w, (const bf16 *)L->ln2_b, d->t_eps, nullptr, 0, 0, 0, (const bf16 *)L->fc1_w, (const bf16 *)L->fc1_b, nullptr,
                         0, b.ffn, Ft, 0, (int)M, Ft, D, 2, 1.0f, 0, s));
     return launch_gemv_rows(0, b.ffn, Ft, nullptr, nullptr, 0.f, nullptr, 0, 0, 0, (const bf16 *)L->fc2_w, (const bf16 *)L->fc2_b, b.h, D, b.h, D, 0, (int)M, D, Ft,
@@ -699,6 +663,68 @@ int opt_rows_head(const EilevDims *d, const EilevOptWeights *w, const OptBufs &b
     const int D = d->t_hidden;
     return launch_gemv_rows(1, b.h, D, (const bf16 *)w->final_ln_w, (const bf16 *)w->final_ln_b, d->t_eps, nullptr, 0, 0, 0, (const bf16 *)w->embed_tokens, nullptr,
                             nullptr, 0, logits, d->vocab, 1, (int)M, d->vocab, D, 0, 1.0f, 0, s);
+}
+// final_layer_norm rows (b.x) -> fp32 logits on the MFMA kernels (17..32 rows: the stream-layout copy of lm_head, where the caller packed it)
+GemmArgs opt_lm_head(const EilevDims *d, const EilevOptWeights *w, const OptBufs &b, int64_t M, float *logits) {
+    const int D = d->t_hidden;
+    GemmArgs g = mk_gemm(b.x, D, w->embed_tokens, D, nullptr, nullptr, 0, logits, d->vocab, M, d->vocab, D, 0);
+    g.out_f32 = 1; g.scratch = b.scratch; g.scratch_bytes = kSkinnyScratch / 2;
+    if (w->lm_head_stream && M > 16 && M <= 32) g.Wp = (const bf16 *)w->lm_head_stream;
+    return g;
+}
+// a decode attention of the q rows in `qkv` into `out`, its flash-decoding partials in the second half of the skinny scratch
+DecodeAttnArgs decode_attn_args(const bf16 *qkv, bf16 *out, float *scratch, int64_t batch, int heads, int hd) {
+    DecodeAttnArgs a;
+    a.qkv = qkv; a.out = out; a.batch = (int)batch; a.heads = heads; a.hd = hd;
+    a.part = scratch + kSkinnyScratch / 2 / sizeof(float); a.part_bytes = kSkinnyScratch / 2;
+    return a;
+}
+// the attention of block l, `a` that of block 0: its caches hold one block every kv_layer elements (the generation cache: gen_layer)
+DecodeAttnArgs at_block(DecodeAttnArgs a, int l, size_t kv_layer, size_t gen_layer) {
+    a.kc += l * kv_layer; a.vc += l * kv_layer;
+    if (a.kg) { a.kg += l * gen_layer; a.vg += l * gen_layer; }
+    return a;
+}
+// The blocks and the LM head of an OPT decode step of M rows, b.h (the embedded tokens) -> fp32 logits, `a` the attention of block 0: 2..4
+// rows on gemvm_kernel (one_pass: attn_decode1_kernel), <= 2 on the row-dot kernels (the attention's partials merged in out_proj's
+// prologue), more on the MFMA kernels (frag: their activations in the row-block layout).  The step's tail is the caller's.
+int opt_decode_blocks(const EilevDims *d, const EilevOptWeights *w, const OptBufs &b, int64_t M, const DecodeAttnArgs &a, size_t kv_layer,
+                      size_t gen_layer, bool one_pass, int frag, float *logits, hipStream_t s) {
+    if (opt_rowsm_usable(d, w, M)) {  // round 4
+        for (int l = 0; l < d->t_layers; ++l) {
+            const DecodeAttnArgs al = at_block(a, l, kv_layer, gen_layer);
+            RC(opt_rowsm_qkv(d, w, l, b, M, s));
+            RC(one_pass ? launch_attn_decode1(al, s) : launch_attn_decode(al, s));
+            RC(opt_rowsm_tail(d, w, l, b, M, s));
+        }
+        return opt_rowsm_head(d, w, b, M, logits, s);
+    }
+    if (opt_rows_usable(d, w, M)) {  // row-dot kernels with LayerNorm / merge in their prologues (gemv.hip): 5 launches + attention per block
+        for (int l = 0; l < d->t_layers; ++l) {
+            DecodeAttnArgs al = at_block(a, l, kv_layer, gen_layer);
+            al.out = nullptr;
+            int nsplit = 0;
+            RC(opt_rows_qkv(d, w, l, b, M, s));
+            RC(launch_attn_decode(al, s, &nsplit));
+            RC(opt_rows_tail(d, w, l, b, M, al.part, nsplit, s));
+        }
+        return opt_rows_head(d, w, b, M, logits, s);
+    }
+    const int D = d->t_hidden;
+    for (int l = 0; l < d->t_layers; ++l) {
+        const EilevOptLayer *L = &w->layers[l];
+        DecodeAttnArgs al = at_block(a, l, kv_layer, gen_layer);
+        al.out_frag = frag;
+        if (l == 0) RC(launch_layernorm(b.h, D, (const bf16 *)L->ln1_w, (const bf16 *)L->ln1_b, b.x, D, M, D, d->t_eps, s));
+        RC(opt_qkv(d, w, l, b, M, s, l > 0 ? frag : 0));
+        RC(launch_attn_decode(al, s));
+        // the block's output goes straight into the LayerNorm that reads it next (the next block's, or final_layer_norm): b.x
+        const bool last = l + 1 == d->t_layers;
+        RC(opt_tail(d, w, l, b, M, s, last ? w->final_ln_w : w->layers[l + 1].ln1_w, last ? w->final_ln_b : w->layers[l + 1].ln1_b, frag));
+    }
+    GemmArgs g = opt_lm_head(d, w, b, M, logits);
+    g.a_frag = frag;
+    return launch_gemm(g, 5, s);
 }
 
 }  // namespace
@@ -865,20 +891,23 @@ extern "C" int eilev_opt_decode_step(const EilevDims *d, const EilevOptWeights *
     RC(launch_decode_embed((const bf16 *)w->embed_tokens, (const bf16 *)w->embed_positions, tokens, n_valid, state, d->vocab,
                            d->max_pos + 1, b.h, (int)batch, D, s));
     const size_t per_layer = (size_t)2 * batch * H * kv_capacity * hd;
+    DecodeAttnArgs a = decode_attn_args(b.qkv, b.att, b.scratch, batch, H, hd);  // block 0's: the cache holds [layers][k | v][batch][heads][kv_capacity][hd]
+    a.kc = (const bf16 *)kv_cache; a.vc = a.kc + per_layer / 2; a.attn_mask = attn_mask; a.state = state; a.seq_len = (int)seq_len; a.cap = (int)kv_capacity;
+    a.fuse_new = 1;  // the new token's K / V go into the cache inside the attention kernel: one launch less per block
     if (opt_rows1_usable(d, w, batch, kv_capacity)) {  // ONE row (round 4): register-resident activations, one-pass attention: 5 launches per block
         for (int l = 0; l < d->t_layers; ++l) {
             const EilevOptLayer *L = &w->layers[l];
-            bf16 *kc = (bf16 *)kv_cache + l * per_layer, *vc = kc + per_layer / 2;
+            const DecodeAttnArgs al = at_block(a, l, per_layer, 0);
             const int Ft = d->t_ffn;
             RC(launch_gemv1(1, b.h, (const bf16 *)L->ln1_w, (const bf16 *)L->ln1_b, d->t_eps, (const bf16 *)L->q_w, (const bf16 *)L->q_b, nullptr, b.qkv, 0, 3 * D, D, 0,
                             1.0f / sqrtf((float)hd), D, s));
             if (hd == 80 && g_decode_rows != 5) {  // 128-key splits over all CUs, merged in out_proj's prologue (eilev_debug_decode_rows(5): one workgroup per head)
-                float *part = b.scratch + kSkinnyScratch / 2 / sizeof(float);
-                RC(launch_attn_decode_part(b.qkv, kc, vc, part, kSkinnyScratch / 2, attn_mask, state, 1, (int)seq_len, (int)kv_capacity, H, hd, s));
-                RC(launch_gemv1(2, nullptr, nullptr, nullptr, 0.f, (const bf16 *)L->o_w, (const bf16 *)L->o_b, b.h, b.h, 0, D, D, 0, 1.0f, 0, s, part, H, hd,
-                                attn_decode_part_splits((int)kv_capacity)));
+                int nsplit = 0;
+                RC(launch_attn_decode_part(al, s, &nsplit));
+                RC(launch_gemv1(2, nullptr, nullptr, nullptr, 0.f, (const bf16 *)L->o_w, (const bf16 *)L->o_b, b.h, b.h, 0, D, D, 0, 1.0f, 0, s, al.part, H, hd,
+                                nsplit));
             } else {
-                RC(launch_attn_decode1(b.qkv, kc, vc, b.att, attn_mask, state, 1, (int)seq_len, (int)kv_capacity, H, hd, s));
+                RC(launch_attn_decode1(al, s));
                 RC(launch_gemv1(0, b.att, nullptr, nullptr, 0.f, (const bf16 *)L->o_w, (const bf16 *)L->o_b, b.h, b.h, 0, D, D, 0, 1.0f, 0, s));
             }
             RC(launch_gemv1(1, b.h, (const bf16 *)L->ln2_w, (const bf16 *)L->ln2_b, d->t_eps, (const bf16 *)L->fc1_w, (const bf16 *)L->fc1_b, nullptr, b.ffn, 0, Ft, D, 2,
@@ -889,42 +918,12 @@ extern "C" int eilev_opt_decode_step(const EilevDims *d, const EilevOptWeights *
                         D, 0, 1.0f, 0, s));
         return launch_select(logits, 1, d->vocab, state, finished, eos_id, pad_id, tokens, out_tokens, max_new, s);
     }
-    if (opt_rowsm_usable(d, w, batch)) {  // 2..4 rows (round 4)
-        const bool one_pass = attn_decode1_ok((int)batch, (int)kv_capacity, hd);
-        for (int l = 0; l < d->t_layers; ++l) {
-            bf16 *kc = (bf16 *)kv_cache + l * per_layer, *vc = kc + per_layer / 2;
-            RC(opt_rowsm_qkv(d, w, l, b, batch, s));
-            if (one_pass) RC(launch_attn_decode1(b.qkv, kc, vc, b.att, attn_mask, state, (int)batch, (int)seq_len, (int)kv_capacity, H, hd, s));
-            else RC(launch_attn_decode(b.qkv, kc, vc, b.att, attn_mask, state, (int)batch, (int)seq_len, (int)kv_capacity, H, hd,
-                                       b.scratch + kSkinnyScratch / 2 / sizeof(float), kSkinnyScratch / 2, s, 0, nullptr, 0, 0, 1));
-            RC(opt_rowsm_tail(d, w, l, b, batch, s));
-        }
-        RC(opt_rowsm_head(d, w, b, batch, logits, s));
-        return launch_select(logits, (int)batch, d->vocab, state, finished, eos_id, pad_id, tokens, out_tokens, max_new, s);
-    }
-    if (opt_rows_usable(d, w, batch)) {  // M <= 8: row-dot kernels with LayerNorm / merge in their prologues (gemv.hip): 5 launches + attention per block
-        float *part = b.scratch + kSkinnyScratch / 2 / sizeof(float);
-        const int nsplit = (int)((kv_capacity + kDecodeKeys - 1) / kDecodeKeys);
-        const bool fuse_merge = batch <= 2;
-        for (int l = 0; l < d->t_layers; ++l) {
-            bf16 *kc = (bf16 *)kv_cache + l * per_layer, *vc = kc + per_layer / 2;
-            RC(opt_rows_qkv(d, w, l, b, batch, s));
-            RC(launch_attn_decode(b.qkv, kc, vc, fuse_merge ? nullptr : b.att, attn_mask, state, (int)batch, (int)seq_len, (int)kv_capacity, H, hd, part,
-                                  kSkinnyScratch / 2, s, 0, nullptr, 0, 0, 1));
-            RC(opt_rows_tail(d, w, l, b, batch, fuse_merge ? part : nullptr, nsplit, s));
-        }
-        RC(opt_rows_head(d, w, b, batch, logits, s));
-        return launch_select(logits, (int)batch, d->vocab, state, finished, eos_id, pad_id, tokens, out_tokens, max_new, s);
-    }
     // 17..32 rows (round 5): the activations between the kernels of a block (attention rows, LayerNorm rows, fc1 rows) in the row-block layout
     // (common.h frag32_index) when every linear of the block runs on gemm_rows32_kernel and the attention on attn_decode_loop_kernel — a
     // dry run of the block's launches decides; the first q|k|v projection reads the row-major LayerNorm of the embedding rows
-    GemmArgs gh = mk_gemm(b.x, D, w->embed_tokens, D, nullptr, nullptr, 0, logits, d->vocab, batch, d->vocab, D, 0);
-    gh.out_f32 = 1; gh.scratch = b.scratch; gh.scratch_bytes = kSkinnyScratch / 2;
-    if (w->lm_head_stream && batch > 16 && batch <= 32) gh.Wp = (const bf16 *)w->lm_head_stream;
     int frag = 0;
-    if (g_decode_frag && batch > 16 && batch <= 32 && !w->layers_w8 && D % 32 == 0 && d->t_ffn % 32 == 0 &&
-        attn_decode_loop_ok((int)batch, H, hd, (int)kv_capacity, false, b.att, state, 1, nullptr)) {
+    if (g_decode_frag && batch > 16 && batch <= 32 && !w->layers_w8 && D % 32 == 0 && d->t_ffn % 32 == 0 && attn_decode_loop_ok(a)) {
+        GemmArgs gh = opt_lm_head(d, w, b, batch, logits);
         gh.a_frag = 1;
         GemmArgs gq = mk_gemm(b.x, D, w->layers[0].q_w, D, w->layers[0].q_b, nullptr, 0, b.qkv, 3 * D, batch, D, D, 0);  // q, k, v one by one
         gq.scratch = b.scratch; gq.scratch_bytes = kSkinnyScratch / 2; gq.a_frag = 1;
@@ -932,21 +931,8 @@ extern "C" int eilev_opt_decode_step(const EilevDims *d, const EilevOptWeights *
         gq3.N = 3 * D;
         frag = gemm_rows32_takes(gh) && gemm_rows32_takes(gq) && gemm_rows32_takes(gq3) &&
                opt_tail(d, w, 0, b, batch, s, w->final_ln_w, w->final_ln_b, 1, true) == EILEV_OK;
-        gh.a_frag = frag;
     }
-    for (int l = 0; l < d->t_layers; ++l) {
-        const EilevOptLayer *L = &w->layers[l];
-        bf16 *kc = (bf16 *)kv_cache + l * per_layer, *vc = kc + per_layer / 2;
-        if (l == 0) RC(launch_layernorm(b.h, D, (const bf16 *)L->ln1_w, (const bf16 *)L->ln1_b, b.x, D, batch, D, d->t_eps, s));
-        RC(opt_qkv(d, w, l, b, batch, s, l > 0 ? frag : 0));
-        // the new token's K / V go into the cache inside the attention kernel (fuse_new): one launch less per layer
-        RC(launch_attn_decode(b.qkv, kc, vc, b.att, attn_mask, state, (int)batch, (int)seq_len, (int)kv_capacity, H, hd,
-                              b.scratch + kSkinnyScratch / 2 / sizeof(float), kSkinnyScratch / 2, s, 0, nullptr, 0, 0, 1, nullptr, nullptr, nullptr, 1, 0, frag));
-        // the block's output goes straight into the LayerNorm that reads it next (the next block's, or final_layer_norm): b.x
-        const bool last = l + 1 == d->t_layers;
-        RC(opt_tail(d, w, l, b, batch, s, last ? w->final_ln_w : w->layers[l + 1].ln1_w, last ? w->final_ln_b : w->layers[l + 1].ln1_b, frag));
-    }
-    RC(launch_gemm(gh, 5, s));
+    RC(opt_decode_blocks(d, w, b, batch, a, per_layer, 0, attn_decode1_ok((int)batch, (int)kv_capacity, hd), frag, logits, s));
     return launch_select(logits, (int)batch, d->vocab, state, finished, eos_id, pad_id, tokens, out_tokens, max_new, s);
 }
 
@@ -972,58 +958,15 @@ extern "C" int eilev_opt_decode_step_beam(const EilevDims *d, const EilevOptWeig
     const int64_t samples = rows / beams;
     OptBufs b;
     if (!carve_opt(d, rows, workspace, workspace_bytes, b)) return EILEV_E_WORKSPACE;
-    if (attn_decode_scratch_bytes((int)rows, H, hd, (int)(seq_len + gen_capacity)) > kSkinnyScratch / 2) return EILEV_E_WORKSPACE;
+    // block 0's attention: the prompt's keys in kv_prompt [layers][k | v][samples][heads][seq_len][hd], the generated ones in kv_gen (a row per beam slot)
+    const size_t per_p = (size_t)2 * samples * H * seq_len * hd, per_g = (size_t)2 * rows * H * gen_capacity * hd;
+    DecodeAttnArgs a = decode_attn_args(b.qkv, b.att, b.scratch, rows, H, hd);
+    if (attn_decode_part_bytes((int)rows, H, hd, (int)(seq_len + gen_capacity)) > a.part_bytes) return EILEV_E_WORKSPACE;
+    a.kc = (const bf16 *)kv_prompt; a.vc = a.kc + per_p / 2; a.attn_mask = attn_mask; a.state = state; a.seq_len = a.cap = (int)seq_len; a.fuse_new = 1;
+    a.kg = (bf16 *)kv_gen; a.vg = a.kg + per_g / 2; a.anc = ancestors; a.beams = (int)beams; a.cap_g = (int)gen_capacity;
     RC(launch_decode_embed((const bf16 *)w->embed_tokens, (const bf16 *)w->embed_positions, tokens, n_valid, state, d->vocab, d->max_pos + 1, b.h,
                            (int)rows, D, s));
-    const size_t per_p = (size_t)2 * samples * H * seq_len * hd, per_g = (size_t)2 * rows * H * gen_capacity * hd;
-    if (opt_rowsm_usable(d, w, rows)) {  // 2..4 rows (e.g. 4 beams of one sample; 5 beams take the MFMA row kernels), round 4: gemvm_kernel around the beam attention
-        for (int l = 0; l < d->t_layers; ++l) {
-            const bf16 *kc = (const bf16 *)kv_prompt + l * per_p, *vc = kc + per_p / 2;
-            bf16 *kg = (bf16 *)kv_gen + l * per_g, *vg = kg + per_g / 2;
-            RC(opt_rowsm_qkv(d, w, l, b, rows, s));
-            RC(launch_attn_decode(b.qkv, kc, vc, b.att, attn_mask, state, (int)rows, (int)seq_len, (int)seq_len, H, hd,
-                                  b.scratch + kSkinnyScratch / 2 / sizeof(float), kSkinnyScratch / 2, s, 0, nullptr, 0, 0, 1, kg, vg, ancestors, (int)beams,
-                                  (int)gen_capacity));
-            RC(opt_rowsm_tail(d, w, l, b, rows, s));
-        }
-        RC(opt_rowsm_head(d, w, b, rows, logits, s));
-        bump_step_kernel<<<1, 64, 0, s>>>(state);
-        EILEV_LAUNCH_CHECK();
-        return EILEV_OK;
-    }
-    if (opt_rows_usable(d, w, rows)) {  // <= 8 rows (the sample script: 5 beams of one sample): the small-batch block of gemv.hip
-        float *part = b.scratch + kSkinnyScratch / 2 / sizeof(float);
-        const int nsplit = (int)((seq_len + gen_capacity + kDecodeKeys - 1) / kDecodeKeys);
-        const bool fuse_merge = rows <= 2;
-        for (int l = 0; l < d->t_layers; ++l) {
-            const bf16 *kc = (const bf16 *)kv_prompt + l * per_p, *vc = kc + per_p / 2;
-            bf16 *kg = (bf16 *)kv_gen + l * per_g, *vg = kg + per_g / 2;
-            RC(opt_rows_qkv(d, w, l, b, rows, s));
-            RC(launch_attn_decode(b.qkv, kc, vc, fuse_merge ? nullptr : b.att, attn_mask, state, (int)rows, (int)seq_len, (int)seq_len, H, hd, part,
-                                  kSkinnyScratch / 2, s, 0, nullptr, 0, 0, 1, kg, vg, ancestors, (int)beams, (int)gen_capacity));
-            RC(opt_rows_tail(d, w, l, b, rows, fuse_merge ? part : nullptr, nsplit, s));
-        }
-        RC(opt_rows_head(d, w, b, rows, logits, s));
-        bump_step_kernel<<<1, 64, 0, s>>>(state);
-        EILEV_LAUNCH_CHECK();
-        return EILEV_OK;
-    }
-    for (int l = 0; l < d->t_layers; ++l) {
-        const EilevOptLayer *L = &w->layers[l];
-        const bf16 *kc = (const bf16 *)kv_prompt + l * per_p, *vc = kc + per_p / 2;
-        bf16 *kg = (bf16 *)kv_gen + l * per_g, *vg = kg + per_g / 2;
-        if (l == 0) RC(launch_layernorm(b.h, D, (const bf16 *)L->ln1_w, (const bf16 *)L->ln1_b, b.x, D, rows, D, d->t_eps, s));
-        RC(opt_qkv(d, w, l, b, rows, s));
-        RC(launch_attn_decode(b.qkv, kc, vc, b.att, attn_mask, state, (int)rows, (int)seq_len, (int)seq_len, H, hd,
-                              b.scratch + kSkinnyScratch / 2 / sizeof(float), kSkinnyScratch / 2, s, 0, nullptr, 0, 0, 1, kg, vg, ancestors, (int)beams,
-                              (int)gen_capacity));
-        const bool last = l + 1 == d->t_layers;
-        RC(opt_tail(d, w, l, b, rows, s, last ? w->final_ln_w : w->layers[l + 1].ln1_w, last ? w->final_ln_b : w->layers[l + 1].ln1_b));
-    }
-    GemmArgs g = mk_gemm(b.x, D, w->embed_tokens, D, nullptr, nullptr, 0, logits, d->vocab, rows, d->vocab, D, 0);
-    g.out_f32 = 1; g.scratch = b.scratch; g.scratch_bytes = kSkinnyScratch / 2;
-    if (w->lm_head_stream && rows > 16 && rows <= 32) g.Wp = (const bf16 *)w->lm_head_stream;
-    RC(launch_gemm(g, 5, s));
+    RC(opt_decode_blocks(d, w, b, rows, a, per_p, per_g, false, 0, logits, s));
     bump_step_kernel<<<1, 64, 0, s>>>(state);  // the step counter lives on the device: a captured step replays for every step
     EILEV_LAUNCH_CHECK();
     return EILEV_OK;
@@ -1385,10 +1328,14 @@ static int t5_decode_impl(const EilevT5Dims *d, const EilevT5Weights *w, const i
     RC(launch_t5_rel_table((const bf16 *)w->dec_rel_bias, b.rel, (int)total, (int)total - 1, H, 0, d->rel_buckets, d->rel_max_dist, s,
                            state));
     const size_t splane = (size_t)batch * H * kv_capacity * hd, cplane = (size_t)batch * H * enc_len * hd;
-    // single-query steps use the split decode-attention kernel; its partials live in the second half of the skinny scratch
-    const size_t skinny_f = kSkinnyScratch / 2 / sizeof(float);
+    // single-query steps: the decode-attention kernels (the self-attention over keys 0 .. total - 1 of the cache, the bias of one query row)
+    DecodeAttnArgs sa = decode_attn_args(b.qkv, b.att, b.scratch, batch, H, hd), ca = sa;
+    sa.ldq = 3 * (int64_t)I; sa.attn_mask = dec_mask; sa.cap = (int)kv_capacity; sa.rel_tab = b.rel; sa.rel_hs = total;
+    // with `state`: kv_total = 1 + state[0] on the device, the table is this query's row (entry j = key j), the kernel stores the new K / V
+    sa.state = state; sa.seq_len = state ? 1 : (int)total; sa.rel_off = state ? -1 : (int)total - 1; sa.fuse_new = state ? 1 : 0;
+    ca.ldq = I; ca.attn_mask = enc_mask; ca.seq_len = ca.cap = (int)enc_len;
     const int64_t kmax = kv_capacity > enc_len ? kv_capacity : enc_len;
-    const bool single = new_len == 1 && attn_decode_scratch_bytes((int)batch, H, hd, (int)kmax) <= kSkinnyScratch / 2;
+    const bool single = new_len == 1 && attn_decode_part_bytes((int)batch, H, hd, (int)kmax) <= sa.part_bytes;
     if (state && !single) return EILEV_E_UNSUPPORTED;
     const size_t hid_bytes = (size_t)M * D * sizeof(bf16);
     const bool fuse_norm = single && M <= 32 && !hidden_out;  // the weight-streaming GEMVs of a decode step (their reduce can carry a norm)
@@ -1408,13 +1355,8 @@ static int t5_decode_impl(const EilevT5Dims *d, const EilevT5Weights *w, const i
             RC(launch_rows_to_cache(b.qkv, 3 * I, 2 * I, vc, (int)batch, (int)new_len, H, hd, (int)kv_capacity, (int)past_len, s, state));
         }
         if (single) {
-            // one query row per sequence: flash-decoding split kernel (keys 0 .. total - 1 of the cache, bias of a single row)
-            if (state)  // kv_total = 1 + state[0] on the device; the table is this query's row (entry j = key j)
-                RC(launch_attn_decode(b.qkv, kc, vc, b.att, nullptr, state, (int)batch, 1, (int)kv_capacity, H, hd, b.scratch + skinny_f,
-                                      kSkinnyScratch / 2, s, 3 * (int64_t)I, b.rel, total, -1, 1));
-            else
-                RC(launch_attn_decode(b.qkv, kc, vc, b.att, dec_mask, nullptr, (int)batch, (int)total, (int)kv_capacity, H, hd,
-                                      b.scratch + skinny_f, kSkinnyScratch / 2, s, 3 * (int64_t)I, b.rel, total, (int)total - 1));
+            sa.kc = kc; sa.vc = vc;
+            RC(launch_attn_decode(sa, s));
         } else {
         AttnArgs a;
             a.q = b.qkv; a.k = kc; a.v = vc; a.o = b.att;
@@ -1436,8 +1378,8 @@ static int t5_decode_impl(const EilevT5Dims *d, const EilevT5Weights *w, const i
         if (!fuse_norm) RC(launch_rmsnorm(b.h, D, (const bf16 *)L->ln_ca, b.x, D, M, D, d->eps, s));
         RC(launch_gemm(t5_gemm(b, b.x, D, L->cq_w, D, nullptr, 0, b.qkv, I, M, I, D), 5, s));
         if (single) {
-            RC(launch_attn_decode(b.qkv, ck, cv, b.att, enc_mask, nullptr, (int)batch, (int)enc_len, (int)enc_len, H, hd, b.scratch + skinny_f,
-                                  kSkinnyScratch / 2, s, (int64_t)I));
+            ca.kc = ck; ca.vc = cv;
+            RC(launch_attn_decode(ca, s));
         } else {
         AttnArgs c;
             c.q = b.qkv; c.k = ck; c.v = cv; c.o = b.att;
