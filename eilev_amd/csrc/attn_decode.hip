@@ -614,3 +614,39 @@ int launch_attn_decode_part(const DecodeAttnArgs &a, hipStream_t s, int *nsplit)
     *nsplit = ns;
     return EILEV_OK;
 }
+
+#ifdef EILEV_PROBES
+// probe / test entry (tests/test_hip_attn_decode.py): ONE launch of a decode-attention launcher on the caller's buffers.  The struct is
+// DecodeAttnArgs field by field as plain pointers and integers (the ctypes mirror lives with the tests); struct_bytes must be its size, so
+// a stale mirror is refused instead of run.  launcher: 0 launch_attn_decode, 1 launch_attn_decode1, 2 launch_attn_decode_part.
+struct EilevDebugAttnDecodeArgs {
+    const void *qkv; int64_t ldq;
+    const void *kc, *vc;
+    void *out;
+    const int32_t *attn_mask, *state;
+    int32_t batch, seq_len, cap, heads, hd, fuse_new;
+    float *part; uint64_t part_bytes;
+    const float *rel_tab; int64_t rel_hs; int32_t rel_off, beams;
+    void *kg, *vg;
+    const int32_t *anc;
+    int32_t cap_g, out_frag;
+};
+extern "C" int eilev_debug_attn_decode(const EilevDebugAttnDecodeArgs *args, size_t struct_bytes, int launcher, int *nsplit_out, void *stream) {
+    if (!args || struct_bytes != sizeof(EilevDebugAttnDecodeArgs) || launcher < 0 || launcher > 2) return EILEV_E_BADARG;
+    DecodeAttnArgs a;
+    a.qkv = (const bf16 *)args->qkv; a.ldq = args->ldq;
+    a.kc = (const bf16 *)args->kc; a.vc = (const bf16 *)args->vc;
+    a.out = (bf16 *)args->out;
+    a.attn_mask = args->attn_mask; a.state = args->state;
+    a.batch = args->batch; a.seq_len = args->seq_len; a.cap = args->cap; a.heads = args->heads; a.hd = args->hd; a.fuse_new = args->fuse_new;
+    a.part = args->part; a.part_bytes = (size_t)args->part_bytes;
+    a.rel_tab = args->rel_tab; a.rel_hs = args->rel_hs; a.rel_off = args->rel_off; a.beams = args->beams;
+    a.kg = (bf16 *)args->kg; a.vg = (bf16 *)args->vg;
+    a.anc = args->anc;
+    a.cap_g = args->cap_g; a.out_frag = args->out_frag;
+    hipStream_t s = (hipStream_t)stream;
+    if (launcher == 1) return launch_attn_decode1(a, s);
+    if (launcher == 2) return nsplit_out ? launch_attn_decode_part(a, s, nsplit_out) : EILEV_E_BADARG;
+    return launch_attn_decode(a, s, nsplit_out);
+}
+#endif

@@ -290,7 +290,9 @@ int eilev_linear_lnfold(const void *a, const void *w_f, const void *bias_f, cons
  *   eilev_debug_beam_part : int (int)         0: beam-search attention at <= 8 rows through the 256-key split kernel (round 3); 1 (default): 128-key ranges
  *   eilev_debug_attn_part32 : int (int)       plain decode attention of head size 80: 0 the 256-key split kernel; 1 (default) by batch size; 2 / 3 force the 256-key ranges / the per-head loop
  *   eilev_debug_vit_head_major : int (int)    0: row-major q|k|v rows in every ViT launch; 1 (default): per-head blocks in launches of >= 512 frames (layers_fold_hm)
- *   eilev_debug_decode_frag : int (int)       0: row-major activations inside the 17..32-row decode step; 1 (default): the row-block layout where every kernel of the block supports it */
+ *   eilev_debug_decode_frag : int (int)       0: row-major activations inside the 17..32-row decode step; 1 (default): the row-block layout where every kernel of the block supports it
+ *   eilev_debug_attn_decode : int (const struct*, size_t, int, int*, void*)  one decode-attention launch on the caller's buffers: the fields of DecodeAttnArgs as a flat struct
+ *                                             whose size must match, launcher 0 / 1 / 2 = launch_attn_decode / launch_attn_decode1 / launch_attn_decode_part (tests/test_hip_attn_decode.py) */
 
 /* fp8 ACTIVATIONS x fp8 weights on the fp8 MFMA (BASELINE configs[4] "fp8 MFMA weights"; v_mfma_f32_32x32x64_f8f6f4, twice the
  * bf16 MFMA rate).  The reference has no fp8 path; parity is against the oracle on the same quantised operands.
