@@ -829,13 +829,8 @@ extern "C" int eilev_attention_dropout(const void *q, const void *k, const void 
                                        float dropout_p, uint32_t seed, void *stream) {
     if (!q || !k || !v || !o || batch <= 0 || heads <= 0 || sq <= 0 || skv <= 0 || !(dropout_p >= 0.0f && dropout_p < 1.0f)) return EILEV_E_BADARG;
     if (rel_tab && (rel_n <= 0 || rel_stride < rel_n)) return EILEV_E_BADARG;
-    AttnArgs a;
-    a.q = (const bf16 *)q; a.k = (const bf16 *)k; a.v = (const bf16 *)v; a.o = (bf16 *)o;
-    a.q_bs = sq * ldq; a.k_bs = skv * ldk; a.v_bs = skv * ldv; a.o_bs = sq * heads * head_dim;
-    a.q_hs = a.k_hs = a.v_hs = a.o_hs = head_dim;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = heads * head_dim;
-    a.batch = (int)batch; a.heads = (int)heads; a.sq = (int)sq; a.skv = (int)skv; a.hd = (int)head_dim; a.scale = scale;
-    a.causal = causal; a.key_mask = key_mask; a.mask_ld = skv; a.dbg = 0;
+    AttnArgs a = attn_rows((const bf16 *)q, ldq, (const bf16 *)k, ldk, (const bf16 *)v, ldv, (bf16 *)o, batch, heads, sq, skv, head_dim, scale);
+    a.causal = causal; a.key_mask = key_mask; a.mask_ld = skv;
     a.rel_tab = rel_tab; a.rel_hs = rel_stride; a.rel_off = (int)rel_off; a.rel_n = (int)rel_n;
     if (dropout_p > 0.0f) {
         a.drop_thr = eilev_drop_threshold(dropout_p); a.drop_seed = seed; a.drop_scale = 1.0f / (1.0f - dropout_p);

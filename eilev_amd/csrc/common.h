@@ -437,7 +437,7 @@ struct AttnArgs {
     int causal;
     const int32_t *key_mask;         // (batch, mask_ld) or null
     int64_t mask_ld;
-    int dbg;                         // probe-only
+    int dbg = 0;                     // probe-only: launch_attention sets it
     // T5 relative position bias (additive, before the softmax): bias(h, i, j) = rel_tab[h * rel_hs + (j - i - (skv - sq)) +
     // rel_off], a per-head table over the relative distance (built by launch_t5_rel_table); null = none
     const float *rel_tab = nullptr;
@@ -451,6 +451,29 @@ struct AttnArgs {
     uint32_t drop_thr = 0, drop_seed = 0;
     float drop_scale = 1.0f;
 };
+// The two layouts an attention is launched on; both return a fully initialised AttnArgs (no mask, not causal, no bias, no dropout) whose
+// output is the dense [batch * sq][heads * hd] matrix `o`.  What is special about a launch (mask, causal, ...) is the caller's to set.
+// Rows: q / k / v are columns of row-major activation buffers (row strides ldq / ldk / ldv; a head every hd elements), sq query and skv key
+// rows per batch entry.
+static inline AttnArgs attn_rows(const bf16 *q, int64_t ldq, const bf16 *k, int64_t ldk, const bf16 *v, int64_t ldv, bf16 *o, int64_t batch,
+                                 int64_t heads, int64_t sq, int64_t skv, int64_t hd, float scale) {
+    AttnArgs a;
+    a.q = q; a.k = k; a.v = v; a.o = o;
+    a.q_bs = sq * ldq; a.k_bs = skv * ldk; a.v_bs = skv * ldv; a.o_bs = sq * heads * hd;
+    a.q_hs = a.k_hs = a.v_hs = a.o_hs = hd;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = heads * hd;
+    a.batch = (int)batch; a.heads = (int)heads; a.sq = (int)sq; a.skv = (int)skv; a.hd = (int)hd; a.scale = scale; a.causal = 0;
+    a.key_mask = nullptr; a.mask_ld = 0;
+    return a;
+}
+// Cache planes: the queries are rows as above, keys and values the planes [batch][heads][cap][hd] of a KV cache, slots [0, skv) of each.
+static inline AttnArgs attn_cache(const bf16 *q, int64_t ldq, const bf16 *kplane, const bf16 *vplane, int64_t cap, bf16 *o, int64_t batch,
+                                  int64_t heads, int64_t sq, int64_t skv, int64_t hd, float scale) {
+    AttnArgs a = attn_rows(q, ldq, kplane, hd, vplane, hd, o, batch, heads, sq, skv, hd, scale);
+    a.k_bs = a.v_bs = heads * cap * hd;
+    a.k_hs = a.v_hs = cap * hd;
+    return a;
+}
 int launch_attention(const AttnArgs &a, hipStream_t s);
 
 // attn_decode.hip: the single query of a decode step per (row, head) against a KV cache.  Host side only: the launchers choose a kernel and

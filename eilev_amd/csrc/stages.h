@@ -1,0 +1,99 @@
+// stages.h — what the stage-orchestration units (vision.hip, opt.hip, t5.hip, blocks.hip) share.  They are the C ABI of include/eilev.h on
+// top of the gfx950 kernels: which kernel runs on which buffer; no arithmetic lives in them.  Every launch goes to the caller's stream,
+// nothing allocates or synchronises (except eilev_prof_collect), so a whole stage can be captured into a hipGraph by the caller.
+#pragma once
+#include "common.h"
+
+#define RC(expr)                 \
+    do {                         \
+        int _rc = (expr);        \
+        if (_rc != 0) return _rc; \
+    } while (0)
+
+// Buffers taken one after the other from a workspace, each aligned to 256 bytes.  base == nullptr: a dry run that only adds up — a stage's
+// *_workspace_bytes function runs the same carve as its forward function, so a buffer is named once.
+struct Carver {
+    char *base;
+    size_t used = 0;
+    template <typename T>
+    T *take(size_t n) {
+        T *q = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += align_up(n * sizeof(T), 256);
+        return q;
+    }
+};
+
+static inline GemmArgs mk_gemm(const bf16 *A, int64_t lda, const void *W, int64_t ldw, const void *bias, const bf16 *resid, int64_t ldr,
+                               void *C, int64_t ldc, int64_t M, int N, int K, int epi) {
+    GemmArgs g;
+    g.A = A; g.lda = lda; g.W = (const bf16 *)W; g.ldw = ldw; g.bias = (const bf16 *)bias; g.resid = resid; g.ldr = ldr;
+    g.C = C; g.ldc = ldc; g.M = (int)M; g.N = N; g.K = K; g.epi = epi; g.out_f32 = 0; g.scale = 1.0f; g.scale_cols = 0;
+    g.patch_group = 0; g.scratch = nullptr; g.scratch_bytes = 0; g.dbg = 0;
+    return g;
+}
+
+// The skinny scratch of the language models' workspaces, in halves: split-K partials of the decode GEMVs | flash-decoding partials (batch 32
+// x 40 heads x 9 key splits x (128 + 2) floats = 6 MB)
+constexpr size_t kSkinnyScratch = 16u << 20, kSkinnyHalf = kSkinnyScratch / 2;
+// mk_gemm with the split-K half of `scratch` attached
+static inline GemmArgs sk_gemm(float *scratch, const bf16 *A, int64_t lda, const void *W, int64_t ldw, const void *bias, const bf16 *resid,
+                               int64_t ldr, void *C, int64_t ldc, int64_t M, int N, int K, int epi) {
+    GemmArgs g = mk_gemm(A, lda, W, ldw, bias, resid, ldr, C, ldc, M, N, K, epi);
+    g.scratch = scratch;
+    g.scratch_bytes = kSkinnyHalf;
+    return g;
+}
+// a decode attention of the q rows in `qkv` into `out`, its flash-decoding partials in the second half of `scratch`
+static inline DecodeAttnArgs decode_attn_args(const bf16 *qkv, bf16 *out, float *scratch, int64_t batch, int heads, int hd) {
+    DecodeAttnArgs a;
+    a.qkv = qkv; a.out = out; a.batch = (int)batch; a.heads = heads; a.hd = hd;
+    a.part = scratch + kSkinnyHalf / sizeof(float); a.part_bytes = kSkinnyHalf;
+    return a;
+}
+
+// A KV cache of bf16 elements, [layers][k | v][batch][heads][cap][hd]; `width` = heads * hd
+struct KvCache {
+    size_t plane;  // the keys (or the values) of one layer
+    KvCache(int64_t batch, int64_t width, int64_t cap) : plane((size_t)batch * cap * width) {}
+    size_t per_layer() const { return 2 * plane; }
+    size_t bytes(int layers) const { return (size_t)layers * per_layer() * sizeof(bf16); }
+    template <typename T>
+    T *k(T *cache, int l) const { return cache + l * per_layer(); }
+    template <typename T>
+    T *v(T *cache, int l) const { return cache + l * per_layer() + plane; }
+};
+
+// the n bf16 arrays p[0], p[1], ... of `each` elements sit back to back in memory (the engine packs q | k | v and k | v so): one GEMM can take
+// them as one matrix, or one bias vector
+static inline bool packed(const void *const *p, int n, size_t each) {
+    for (int i = 1; i < n; ++i)
+        if ((const bf16 *)p[i] != (const bf16 *)p[0] + i * each) return false;
+    return true;
+}
+
+// one snapshot of the residual stream (`bytes` bytes) into slot i of a hidden-states output
+static inline int copy_hidden(void *hidden_states, int64_t i, const void *x, size_t bytes, hipStream_t s) {
+    EILEV_HIP_CHECK(hipMemcpyAsync((char *)hidden_states + i * bytes, x, bytes, hipMemcpyDeviceToDevice, s));
+    return EILEV_OK;
+}
+
+static inline bool dims_ok_vit(const EilevDims *d) {
+    return d->v_hidden % 8 == 0 && d->v_inter % 8 == 0 && d->v_heads > 0 && d->v_hidden % d->v_heads == 0 &&
+           (d->v_hidden / d->v_heads) % 8 == 0 && d->v_hidden / d->v_heads <= 128 && d->v_hidden <= 4096 &&
+           d->image_size % d->patch_size == 0;
+}
+static inline bool dims_ok_qf(const EilevDims *d) {
+    return d->q_hidden % 8 == 0 && d->q_inter % 8 == 0 && d->q_heads > 0 && d->q_hidden % d->q_heads == 0 &&
+           (d->q_hidden / d->q_heads) % 8 == 0 && d->q_hidden / d->q_heads <= 128 && d->q_hidden <= 4096 && d->q_cross_freq > 0;
+}
+static inline bool dims_ok_opt(const EilevDims *d) {
+    return d->t_hidden % 8 == 0 && d->t_ffn % 8 == 0 && d->t_heads > 0 && d->t_hidden % d->t_heads == 0 &&
+           (d->t_hidden / d->t_heads) % 8 == 0 && d->t_hidden / d->t_heads <= 128 && d->t_hidden <= 4096;
+}
+static inline bool dims_ok_t5(const EilevT5Dims *d) {
+    return d->d_model % 8 == 0 && d->d_kv % 8 == 0 && d->d_kv <= 128 && d->heads > 0 && d->d_ff % 8 == 0 && d->d_model <= 4096 &&
+           d->rel_buckets >= 4 && d->rel_max_dist > d->rel_buckets / 4;
+}
+
+// probe / test switches read outside the unit that defines them (set by eilev_debug_* of the probe build)
+extern int g_decode_rows;  // opt.hip; eilev_linear_rows (blocks.hip) follows it
