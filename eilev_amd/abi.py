@@ -561,6 +561,59 @@ def load_pld() -> C.CDLL:
     return _pld
 
 
+# ---- the device-sampling companion library (include/eilev_sample.h): a third shared library with its own exports, loaded on demand ----
+SAMPLE_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_sample.so")
+SAMPLE_ABI_VERSION = 1
+SAMPLE_MAX_EOS = 8
+SAMPLE_MAX_VOCAB = 65536
+SAMPLE_EXPORTS = ["eilev_sample_abi_version", "eilev_sample_scratch_bytes", "eilev_sample_select"]
+
+
+class SampleParams(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float), ("top_k", C.c_int32),
+                ("min_new", C.c_int64), ("max_new", C.c_int64), ("n_eos", C.c_int64), ("eos", C.c_int64 * SAMPLE_MAX_EOS),
+                ("pad_id", C.c_int64), ("prefix_id", C.c_int64), ("step_offset", C.c_int32), ("finalize", C.c_int32)]
+
+
+def sample_params(temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, min_new=0, max_new=1, eos_ids=(), pad_id=0, prefix_id=-1,
+                  step_offset=0, finalize=1) -> SampleParams:
+    eos_ids = [int(e) for e in eos_ids]
+    if len(eos_ids) > SAMPLE_MAX_EOS:
+        raise NotImplementedError(f"device sampling takes at most {SAMPLE_MAX_EOS} EOS ids")
+    p = SampleParams(float(temperature), float(top_p), float(repetition_penalty), int(top_k or 0), int(min_new), int(max_new), len(eos_ids))
+    for i, e in enumerate(eos_ids):
+        p.eos[i] = e
+    p.pad_id, p.prefix_id, p.step_offset, p.finalize = int(pad_id), int(prefix_id), int(step_offset), int(finalize)
+    return p
+
+
+def sample_supported(vocab: int) -> bool:
+    """The vocabulary sizes eilev_sample_select takes (anything else returns EILEV_E_UNSUPPORTED)."""
+    return 0 < int(vocab) <= SAMPLE_MAX_VOCAB and int(vocab) % 4 == 0
+
+
+_sample = None
+
+
+def load_sample() -> C.CDLL:
+    """Load libeilev_hip_sample.so (built next to libeilev_hip.so by build_hip()).  No fallback: a missing build is an error."""
+    global _sample
+    if _sample is None:
+        if not os.path.exists(SAMPLE_LIB_PATH):
+            raise RuntimeError(f"{SAMPLE_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(SAMPLE_LIB_PATH)
+        i64, i32, sz = C.c_int64, C.c_int, C.c_size_t
+        lib.eilev_sample_abi_version.restype = i32
+        lib.eilev_sample_scratch_bytes.restype = sz
+        lib.eilev_sample_scratch_bytes.argtypes = [i64, i64]
+        lib.eilev_sample_select.restype = i32
+        lib.eilev_sample_select.argtypes = [C.POINTER(SampleParams), vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        if lib.eilev_sample_abi_version() != SAMPLE_ABI_VERSION:
+            raise RuntimeError(f"{SAMPLE_LIB_PATH}: ABI version mismatch")
+        _sample = lib
+    return _sample
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         names = {-1: "EILEV_E_BADARG", -2: "EILEV_E_UNSUPPORTED", -3: "EILEV_E_WORKSPACE"}

@@ -1,5 +1,5 @@
-"""Builds eilev_amd/csrc/libeilev_hip.so and its prompt-lookup companion libeilev_hip_pld.so (gfx950) in-tree with hipcc.
-Cross-compiles without a GPU."""
+"""Builds eilev_amd/csrc/libeilev_hip.so and its companions libeilev_hip_pld.so (prompt lookup) and libeilev_hip_sample.so (device
+sampling) (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
 from __future__ import annotations
 
 import os
@@ -17,6 +17,10 @@ LIB = os.path.join(HERE, "libeilev_hip.so")
 PLD_SOURCE = "pld.hip"
 PLD_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_pld.h")]
 PLD_LIB = os.path.join(HERE, "libeilev_hip_pld.so")
+# the device-sampling companion (include/eilev_sample.h), built the same way
+SAMPLE_SOURCE = "sample.hip"
+SAMPLE_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_sample.h")]
+SAMPLE_LIB = os.path.join(HERE, "libeilev_hip_sample.so")
 
 
 def _hipcc() -> str:
@@ -59,20 +63,20 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "", ext
             raise RuntimeError(f"hipcc failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
         return r.stderr
 
-    # the default build (no variant) also builds the companion library; the probe variant does not need it
-    pld_src, pld_map = os.path.join(HERE, PLD_SOURCE), os.path.join(HERE, "exports_pld.map")
-    pld_deps = [pld_src, pld_map] + [os.path.join(HERE, h) for h in PLD_HEADERS]
-    pld_job = None
-    if not variant and (force or _stale(PLD_LIB, pld_deps)):
-        pld_job = [_hipcc(), *FLAGS, *extra_flags, "-shared", "-o", PLD_LIB, pld_src, "-Wl,--version-script=" + pld_map]
+    # the default build (no variant) also builds the companion libraries; the probe variant does not need them
+    side_jobs = []
+    for src, hdr, emap, out in ((PLD_SOURCE, PLD_HEADERS, "exports_pld.map", PLD_LIB), (SAMPLE_SOURCE, SAMPLE_HEADERS, "exports_sample.map", SAMPLE_LIB)):
+        src, emap = os.path.join(HERE, src), os.path.join(HERE, emap)
+        if not variant and (force or _stale(out, [src, emap] + [os.path.join(HERE, h) for h in hdr])):
+            side_jobs.append([_hipcc(), *FLAGS, *extra_flags, "-shared", "-o", out, src, "-Wl,--version-script=" + emap])
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES) + 2) as ex:
-        pld_fut = ex.submit(run, pld_job) if pld_job else None
+    with ThreadPoolExecutor(max_workers=len(SOURCES) + 3) as ex:
+        side_futs = [ex.submit(run, j) for j in side_jobs]
         for warn in ex.map(run, jobs):
             if verbose and warn.strip():
                 print(warn, file=sys.stderr)
-        if pld_fut is not None:
-            warn = pld_fut.result()
+        for fut in side_futs:
+            warn = fut.result()
             if verbose and warn.strip():
                 print(warn, file=sys.stderr)
     if force or jobs or _stale(lib, objs + [os.path.join(HERE, "exports.map")]):

@@ -39,6 +39,8 @@ class HipEngine:
         self.timing = None  # bench.py sets this to a list to collect phase events
         self._decode_warm = False
         self._dec_cache = None  # most recent captured decode step + the buffers it is bound to
+        self.device_sampling = True  # generate(do_sample=True, num_beams=1): the draw runs in the captured step (sample_decode_device); False: the host loop
+        self.sample_stats = None     # per sampling call: dict(path="device" | "host", steps=generated tokens per row)
         self.parts = tuple(parts)
         if lm_weights not in ("bf16", "fp8", "fp8_mfma"):
             raise ValueError("lm_weights must be 'bf16', 'fp8' (e4m3 weights, bf16 activations) or 'fp8_mfma' (e4m3 weights AND per-token "
@@ -814,6 +816,10 @@ class HipEngine:
         R = B * num_beams
         if num_beams > 32:
             raise NotImplementedError("num_beams > 32")
+        if sampler is not None and num_beams == 1:
+            sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id, trace)
+            if dev_kw is not None:
+                return self.sample_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, **dev_kw)
         if R > 32:
             # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are
             # independent in beam search); shorter results are padded with pad_id like HF pads finished hypotheses
@@ -938,15 +944,251 @@ class HipEngine:
         if sampler is not None and num_beams == 1:  # multinomial sampling: eilev_amd/sampling.py on the same decode step
             from .sampling import sample_loop
 
-            return sample_loop(step, last, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
-        return beam_search(step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
-                           num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
+            ids = sample_loop(step, last, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
+            self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
+            return ids
+        ids = beam_search(step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
+                          num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
+        if sampler is not None:  # beam-search sampling
+            self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
+        return ids
 
     def sample_decode(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
-                      generator=None):
-        """`generate(do_sample=True)` [hf generation/utils.py `_sample`]: prefill once, then one HIP decode step per drawn token."""
+                      generator=None, repetition_penalty=1.0, min_new_tokens=0):
+        """`generate(do_sample=True)` [hf generation/utils.py `_sample`]: prefill once, then one HIP decode step per drawn token.  The draw runs
+        on the device in the captured step (sample_decode_device) unless `self.device_sampling` is off or the kernel does not take the call."""
         return self.beam_decode(inputs_embeds, attention_mask, max_new_tokens, 1, eos_id=eos_id, pad_id=pad_id,
-                                sampler=dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator))
+                                sampler=dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator,
+                                             repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens))
+
+    def _route_sampling(self, sampler, rules, vocab, eos_id, trace=None):
+        """Where a `sampler is not None and num_beams == 1` call runs.  Returns (sampler, rules, dev_kw): dev_kw is the keyword set of
+        sample_decode_device / t5_sample_device when the device path takes the call, else None with (sampler, rules) in the form the host
+        loop (eilev_amd/sampling.py sample_loop) takes — a numeric repetition_penalty becomes transformers' processor again."""
+        from .sampling import eos_list
+
+        sampler = dict(sampler)
+        pen = float(sampler.pop("repetition_penalty", None) or 1.0)
+        host_only = bool(rules) and (rules.get("processors") is not None or rules.get("stopping") is not None)
+        if (getattr(self, "device_sampling", True) and not host_only and trace is None and not sampler.get("greedy") and
+                len(eos_list(eos_id)) <= abi.SAMPLE_MAX_EOS and abi.sample_supported(vocab)):
+            return sampler, rules, dict(temperature=sampler.get("temperature", 1.0), top_k=sampler.get("top_k", 50), top_p=sampler.get("top_p", 1.0),
+                                        repetition_penalty=pen, min_new_tokens=sampler.get("min_new_tokens", 0), generator=sampler.get("generator"))
+        if pen != 1.0:
+            from transformers import LogitsProcessorList, RepetitionPenaltyLogitsProcessor
+
+            rules = dict(rules or {})
+            rules["processors"] = LogitsProcessorList([RepetitionPenaltyLogitsProcessor(penalty=pen)] + list(rules.get("processors") or []))
+            rules.setdefault("stopping", None)
+        return sampler, rules, None
+
+    def _sample_setup(self, R, vocab, max_new_tokens, generator, uniforms, **spec):
+        """The sampling library, the uniforms of a whole call — (max_new, R), drawn ONCE on the generator's device — and a function that makes
+        the parameter block of one eilev_sample_select call."""
+        smp = abi.load_sample()
+        if not abi.sample_supported(vocab):
+            raise NotImplementedError(f"device sampling: vocab {vocab} (at most {abi.SAMPLE_MAX_VOCAB}, a multiple of 4)")
+        if uniforms is None:
+            gdev = generator.device if generator is not None else self.device
+            uniforms = torch.rand((max_new_tokens, R), generator=generator, device=gdev, dtype=torch.float32)
+        uniforms = uniforms.to(self.device, torch.float32).contiguous()
+        assert uniforms.shape == (max_new_tokens, R), uniforms.shape
+
+        def params(step_offset, finalize):
+            return abi.sample_params(max_new=max_new_tokens, step_offset=step_offset, finalize=finalize, **spec)
+
+        return smp, uniforms, params
+
+    def _sample_select(self, smp, params, logits, R, vocab, uni, state, finished, tokens, out, scratch, warped=None):
+        abi.check(smp.eilev_sample_select(C.byref(params), _ptr(logits), R, vocab, _ptr(uni), _ptr(state), _ptr(finished), _ptr(tokens), _ptr(out),
+                                          _ptr(warped) if warped is not None else None, _ptr(scratch) if scratch.numel() else None, scratch.numel(),
+                                          self._stream()), "eilev_sample_select")
+
+    def _trim_sampled(self, out, n, eos, pad_id):
+        """The first n columns of `out`, cut where every row has drawn an EOS id (hf stops there); finished rows already hold the pad id."""
+        ids = out[:, :n]
+        if eos:
+            is_eos = torch.isin(ids, torch.tensor(eos, dtype=torch.int64, device=self.device))
+            first = torch.where(is_eos.any(dim=1), is_eos.float().argmax(dim=1) + 1, torch.full((ids.shape[0],), n, device=self.device))
+            ids = ids[:, : int(first.max().item())]
+        return ids.clone()
+
+    def _capture_sample_step(self, one_step, buffers, warm):
+        """One decode-and-draw step as a hipGraph.  ``warm``: run the step once outside capture first (lazy module loading) and put
+        ``buffers`` (the words the step advances) back."""
+        graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            if warm:
+                snap = [b.clone() for b in buffers]
+                one_step()
+                for b, keep in zip(buffers, snap):
+                    b.copy_(keep)
+            with torch.cuda.graph(graph, stream=side):
+                one_step()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        return graph
+
+    def _run_sample_steps(self, n_steps, one_step, graph, state, eos, poll_every, trace, logits, poll_last=False):
+        """Replay (or launch) up to n_steps steps; with EOS ids, read state[1] back every poll_every steps and stop once no row is left.
+        Returns the steps done."""
+        done = 0
+        while done < n_steps:
+            if graph is not None:
+                graph.replay()
+            else:
+                one_step()
+                if trace is not None:
+                    trace.append(logits.clone())
+            done += 1
+            if eos and (done % poll_every == 0 or (poll_last and done == n_steps)) and int(state[1].item()) == 0:
+                break
+        return done
+
+    def sample_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
+                             repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None):
+        """Multinomial sampling with the draw on the device (include/eilev_sample.h): greedy_decode's structure — one KV cache of capacity
+        L + max_new, the stream layout, ONE captured step replayed per token — with eilev_sample_select after the decode step.  The decode
+        step's own arg-max writes to scratch buffers (eos -1); eilev_sample_select then overwrites `tokens`.  ``eos_id``: an id or up to 8 ids.
+        ``trace``: a list that receives a copy of every step's logits (use_graph=False).  ``uniforms``: (max_new, rows) in [0, 1) instead of
+        the ones drawn from ``generator``.  Returns int64 (B, n) new tokens."""
+        from .sampling import eos_list
+
+        d = self.dims
+        B, L, _ = inputs_embeds.shape
+        if max_new_tokens <= 0:
+            return torch.empty((B, 0), dtype=torch.int64, device=self.device)
+        eos = eos_list(eos_id)
+        spec = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos,
+                    pad_id=pad_id, prefix_id=-1)
+        smp, uni_all, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, **spec)
+        if B > 32:  # as greedy_decode: consecutive 32-row decodes, shorter parts padded like hf pads rows that stopped early
+            if trace is not None:
+                raise ValueError("trace: at most 32 decode rows")
+            parts, n_steps = [], 0
+            for i in range(0, B, 32):
+                parts.append(self.sample_decode_device(inputs_embeds[i:i + 32], attention_mask[i:i + 32], max_new_tokens, eos_id, pad_id, temperature, top_k,
+                                                       top_p, repetition_penalty, min_new_tokens, None, use_graph, poll_every, None, uni_all[:, i:i + 32]))
+                n_steps = max(n_steps, self.sample_stats["steps"])
+            n = max(p.shape[1] for p in parts)
+            self.sample_stats = dict(path="device", steps=n_steps)
+            return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
+        cap = L + max_new_tokens
+        n_dec = max_new_tokens - 1
+        if n_dec > 0:
+            self.ensure_stream_layout(B)
+        graphable = use_graph and n_dec > 1 and trace is None
+        # the captured step depends on buffer addresses, on the shape and on the parameter block (passed by value): one cached entry, in
+        # greedy_decode's slot (a call of the other kind replaces it, so one KV cache is kept at a time)
+        key = ("sample", B, L, cap, max_new_tokens, float(temperature), int(top_k or 0), float(top_p), float(repetition_penalty), int(min_new_tokens),
+               tuple(eos), int(pad_id))
+        ent = self._dec_cache if (graphable and self._dec_cache is not None and self._dec_cache["key"] == key) else None
+        if ent is None:
+            ent = dict(key=key, graph=None,
+                       am=torch.empty((B, L), dtype=torch.int32, device=self.device),
+                       n_valid=torch.empty(B, dtype=torch.int32, device=self.device),
+                       kv=self.new_kv_cache(B, cap),
+                       state=torch.zeros(2, dtype=torch.int32, device=self.device),
+                       finished=torch.zeros(B, dtype=torch.uint8, device=self.device),
+                       tokens=torch.zeros(B, dtype=torch.int64, device=self.device),
+                       out=torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device),
+                       uni=torch.empty((max_new_tokens, B), dtype=torch.float32, device=self.device),
+                       argmax_out=torch.zeros((B, max_new_tokens), dtype=torch.int64, device=self.device),   # the decode step's own selection:
+                       argmax_fin=torch.zeros(B, dtype=torch.uint8, device=self.device),                     # never read
+                       scratch=torch.empty(int(smp.eilev_sample_scratch_bytes(B, d.vocab)), dtype=torch.uint8, device=self.device),
+                       logits=torch.empty((B, d.vocab), dtype=torch.float32, device=self.device),
+                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1)))
+            if graphable:
+                self._dec_cache = None  # drop the previous entry (its KV cache) before keeping this one
+                self._dec_cache = ent
+        am, n_valid, kv, uni, scratch = ent["am"], ent["n_valid"], ent["kv"], ent["uni"], ent["scratch"]
+        state, finished, tokens, out, logits, ws = ent["state"], ent["finished"], ent["tokens"], ent["out"], ent["logits"], ent["ws"]
+        am.copy_(attention_mask.to(self.device, torch.int32))
+        n_valid.copy_(am.sum(dim=1))
+        uni.copy_(uni_all)
+        state.zero_()
+        finished.zero_()
+        out.fill_(int(pad_id))
+        last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
+        if self.timing is not None:  # optional phase stamps for bench.py (events on the launch stream, no sync)
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.timing.append(("prefill_done", ev))
+        if trace is not None:
+            trace.append(last.clone())
+        self._sample_select(smp, params(0, 1), last, B, d.vocab, uni, state, finished, tokens, out, scratch)
+        p_step = params(-1, 0)  # (the decode step has already advanced state[0])
+
+        def one_step():
+            abi.check(self.lib.eilev_opt_decode_step(
+                C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), B, L, _ptr(kv), cap,
+                _ptr(logits), _ptr(ent["argmax_fin"]), -1, pad_id, _ptr(ent["argmax_out"]), max_new_tokens, _ptr(ws), ws.numel(),
+                self._stream()), "eilev_opt_decode_step")
+            self._sample_select(smp, p_step, logits, B, d.vocab, uni, state, finished, tokens, out, scratch)
+
+        graph = ent["graph"] if graphable else None
+        if graphable and graph is None:  # (once per engine the step also runs outside capture: lazy module loading of the kernels)
+            graph = ent["graph"] = self._capture_sample_step(one_step, (state, finished, tokens, out), warm=not self._decode_warm)
+            self._decode_warm = True
+        done_steps = self._run_sample_steps(n_dec, one_step, graph, state, eos, poll_every, trace, logits)
+        ids = self._trim_sampled(out, 1 + done_steps, eos, pad_id)
+        self.sample_stats = dict(path="device", steps=int(ids.shape[1]))
+        return ids
+
+    def t5_sample_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, temperature=1.0, top_k=50, top_p=1.0,
+                         repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None):
+        """t5_greedy with eilev_sample_select in place of the arg-max: decoder ids (B, 1 + n) INCLUDING the start token, which the repetition
+        penalty sees (prefix_id), as hf's processors do.  ``trace`` / ``uniforms``: as sample_decode_device."""
+        from .sampling import eos_list
+
+        d = self.t5dims
+        B = inputs_embeds.shape[0]
+        start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
+        if max_new_tokens <= 0:
+            return start
+        eos = eos_list(eos_id)
+        smp, uni, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, temperature=temperature, top_k=top_k, top_p=top_p,
+                                              repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos, pad_id=pad_id,
+                                              prefix_id=int(start_id))
+        if B > 32:  # as sample_decode_device: consecutive 32-row decodes on slices of the same uniforms, shorter parts padded
+            if trace is not None:
+                raise ValueError("trace: at most 32 decode rows")
+            parts, n_steps = [], 0
+            for i in range(0, B, 32):
+                parts.append(self.t5_sample_device(inputs_embeds[i:i + 32], attention_mask[i:i + 32], max_new_tokens, eos_id, pad_id, start_id, temperature,
+                                                   top_k, top_p, repetition_penalty, min_new_tokens, None, use_graph, poll_every, None, uni[:, i:i + 32]))
+                n_steps = max(n_steps, self.sample_stats["steps"])
+            n = max(p.shape[1] for p in parts)
+            self.sample_stats = dict(path="device", steps=n_steps)
+            return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
+        enc = self.t5_encode(inputs_embeds, attention_mask)
+        ckv = self.t5_cross_kv(enc)
+        L = enc.shape[1]
+        cap = max_new_tokens
+        am = attention_mask.to(self.device, torch.int32).contiguous()
+        skv = torch.empty(int(self.lib.eilev_t5_self_kv_bytes(C.byref(d), B, cap)), dtype=torch.uint8, device=self.device)
+        state = torch.zeros(2, dtype=torch.int32, device=self.device)
+        finished = torch.zeros(B, dtype=torch.uint8, device=self.device)
+        tokens = torch.full((B,), int(start_id), dtype=torch.int64, device=self.device)
+        out = torch.full((B, max_new_tokens), int(pad_id), dtype=torch.int64, device=self.device)
+        logits = torch.empty((B, d.vocab), dtype=torch.float32, device=self.device)
+        scratch = torch.empty(int(smp.eilev_sample_scratch_bytes(B, d.vocab)), dtype=torch.uint8, device=self.device)
+        ws = self._workspace("t5dec", self.lib.eilev_t5_workspace_bytes(C.byref(d), B, 1, max(L, cap)))
+        p_step = params(0, 1)
+
+        def one_step():
+            abi.check(self.lib.eilev_t5_decode_step(C.byref(d), C.byref(self.pack.t5), _ptr(tokens), _ptr(state), _ptr(am), B, _ptr(skv), cap,
+                                                    _ptr(ckv), L, _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_t5_decode_step")
+            self._sample_select(smp, p_step, logits, B, d.vocab, uni, state, finished, tokens, out, scratch)
+
+        graph = None
+        if use_graph and max_new_tokens > 1 and trace is None:  # (the warm-up step only touches cache slot 0, which the replay rewrites)
+            graph = self._capture_sample_step(one_step, (state, finished, tokens, out), warm=True)
+        n = self._run_sample_steps(max_new_tokens, one_step, graph, state, eos, poll_every, trace, logits, poll_last=True)
+        ids = self._trim_sampled(out, n, eos, pad_id)
+        self.sample_stats = dict(path="device", steps=int(ids.shape[1]))
+        return torch.cat((start, ids), dim=1)
 
 
     # ---- encoder-decoder LM (flan-t5) ------------------------------------------------------------------------
@@ -1155,6 +1397,13 @@ class HipEngine:
             e = eos_list(eos_id)
             pad_id = e[0] if e else -1
         d = self.t5dims
+        if sampler is not None and num_beams == 1:
+            sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id)
+            if dev_kw is not None:
+                return self.t5_sample_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, start_id=start_id, **dev_kw)
+            if rules and rules.get("processors") is not None and rules.get("prefix") is None:  # hf's processors see the start token
+                rules = dict(rules)  # (the caller's dict stays as it is)
+                rules["prefix"] = torch.full((inputs_embeds.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
         enc = self.t5_encode(inputs_embeds, attention_mask)
         B, L, _ = enc.shape
         R = B * num_beams
@@ -1177,18 +1426,23 @@ class HipEngine:
             from .sampling import sample_loop
 
             ids = sample_loop(step, first, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
+            self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
         else:
             ids = beam_search(step, first[::num_beams].contiguous(), B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id,
                               early_stopping, num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
+            if sampler is not None:  # beam-search sampling
+                self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
         head = torch.full((ids.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
         return torch.cat((head, ids), dim=1)
 
 
     def t5_sample(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, temperature=1.0, top_k=50, top_p=1.0,
-                  generator=None):
-        """`generate(do_sample=True)` for the encoder-decoder LM (the decoder start token in front, like t5_greedy / t5_beam)."""
+                  generator=None, repetition_penalty=1.0, min_new_tokens=0):
+        """`generate(do_sample=True)` for the encoder-decoder LM (the decoder start token in front, like t5_greedy / t5_beam); the draw runs on
+        the device (t5_sample_device) under the conditions of sample_decode."""
         return self.t5_beam(inputs_embeds, attention_mask, max_new_tokens, 1, eos_id=eos_id, pad_id=pad_id, start_id=start_id,
-                            sampler=dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator))
+                            sampler=dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator,
+                                         repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens))
 
 
 def abi_dtype(t: torch.Tensor) -> int:

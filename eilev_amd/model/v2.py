@@ -552,12 +552,17 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
 
         procs = LogitsProcessorList()
         rp = kw.pop("repetition_penalty", None)
-        if rp is not None and float(rp) != 1.0:
-            procs.append(RepetitionPenaltyLogitsProcessor(penalty=float(rp)))
         ngram = kw.pop("no_repeat_ngram_size", None)
+        user_procs = kw.pop("logits_processor", None)
+        if rp is not None and float(rp) != 1.0:
+            if sampler is not None and num_beams == 1 and not ngram and not user_procs:
+                # the only processor of a sampling call: the engine takes it as a number — the device path applies it in the captured step
+                # (include/eilev_sample.h), the host loop wraps it into the same transformers processor (engine._route_sampling)
+                sampler["repetition_penalty"] = float(rp)
+            else:
+                procs.append(RepetitionPenaltyLogitsProcessor(penalty=float(rp)))
         if ngram:
             procs.append(NoRepeatNGramLogitsProcessor(int(ngram)))
-        user_procs = kw.pop("logits_processor", None)
         if user_procs:
             procs.extend(user_procs)
         crit = StoppingCriteriaList(kw.pop("stopping_criteria", None) or [])
