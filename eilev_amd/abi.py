@@ -614,6 +614,65 @@ def load_sample() -> C.CDLL:
     return _sample
 
 
+# ---- the logits-rules companion library (include/eilev_rules.h): a fourth shared library with its own exports, loaded on demand ----
+RULES_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_rules.so")
+RULES_ABI_VERSION = 1
+RULES_MAX_EOS = 8
+RULES_MAX_VOCAB = 65536
+RULES_MAX_KEEP = 64
+RULES_EXPORTS = ["eilev_rules_abi_version", "eilev_rules_ban", "eilev_rules_scratch_bytes", "eilev_rules_select", "eilev_rules_topk_logprob"]
+
+
+class RulesParams(C.Structure):
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram", C.c_int32), ("min_new", C.c_int64), ("max_new", C.c_int64),
+                ("n_eos", C.c_int64), ("eos", C.c_int64 * RULES_MAX_EOS), ("pad_id", C.c_int64), ("prefix_id", C.c_int64),
+                ("step_offset", C.c_int32), ("finalize", C.c_int32)]
+
+
+def rules_params(repetition_penalty=1.0, no_repeat_ngram=0, min_new=0, max_new=1, eos_ids=(), pad_id=0, prefix_id=-1, step_offset=0,
+                 finalize=1) -> RulesParams:
+    eos_ids = [int(e) for e in eos_ids]
+    if len(eos_ids) > RULES_MAX_EOS:
+        raise NotImplementedError(f"the device rules take at most {RULES_MAX_EOS} EOS ids")
+    p = RulesParams(float(repetition_penalty), int(no_repeat_ngram or 0), int(min_new), int(max_new), len(eos_ids))
+    for i, e in enumerate(eos_ids):
+        p.eos[i] = e
+    p.pad_id, p.prefix_id, p.step_offset, p.finalize = int(pad_id), int(prefix_id), int(step_offset), int(finalize)
+    return p
+
+
+def rules_supported(vocab: int) -> bool:
+    """The vocabulary sizes the eilev_rules_* calls take (anything else returns EILEV_E_UNSUPPORTED)."""
+    return 0 < int(vocab) <= RULES_MAX_VOCAB and int(vocab) % 4 == 0
+
+
+_rules = None
+
+
+def load_rules() -> C.CDLL:
+    """Load libeilev_hip_rules.so (built next to libeilev_hip.so by build_hip()).  No fallback: a missing build is an error."""
+    global _rules
+    if _rules is None:
+        if not os.path.exists(RULES_LIB_PATH):
+            raise RuntimeError(f"{RULES_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(RULES_LIB_PATH)
+        i64, i32, sz = C.c_int64, C.c_int, C.c_size_t
+        PP = C.POINTER(RulesParams)
+        lib.eilev_rules_abi_version.restype = i32
+        lib.eilev_rules_scratch_bytes.restype = sz
+        lib.eilev_rules_scratch_bytes.argtypes = [i64, i64]
+        lib.eilev_rules_select.restype = i32
+        lib.eilev_rules_select.argtypes = [PP, vp, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+        lib.eilev_rules_topk_logprob.restype = i32
+        lib.eilev_rules_topk_logprob.argtypes = [PP, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+        lib.eilev_rules_ban.restype = i32
+        lib.eilev_rules_ban.argtypes = [PP, vp, i64, i64, vp, vp, vp]
+        if lib.eilev_rules_abi_version() != RULES_ABI_VERSION:
+            raise RuntimeError(f"{RULES_LIB_PATH}: ABI version mismatch")
+        _rules = lib
+    return _rules
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         names = {-1: "EILEV_E_BADARG", -2: "EILEV_E_UNSUPPORTED", -3: "EILEV_E_WORKSPACE"}

@@ -26,7 +26,8 @@ def _take(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def beam_search_device(step_dev, logits_buf: torch.Tensor, first_logits: torch.Tensor, batch: int, num_beams: int, max_new_tokens: int,
                        length_penalty: float = 1.0, eos_id=-1, pad_id: int = 1, early_stopping=False, num_return_sequences: int = 1,
-                       use_graph: bool = True, check_every: int = 4, topk_fn=None, advance_fn=None, anc_state=None) -> torch.Tensor:
+                       use_graph: bool = True, check_every: int = 4, topk_fn=None, advance_fn=None, anc_state=None,
+                       topk_history: bool = False) -> torch.Tensor:
     """The plain beam search of `beam_search` (no sampler, processors, stopping criteria or minimum length: the sample script's call,
     ref:samples/eilev_generate_action_narration.py:60-73) with NOTHING per step on the host: the step index lives on the device, every
     slice by it is an index tensor, the hypotheses are updated in place — so selection + ancestor-table update + the HIP decode step
@@ -43,7 +44,12 @@ def beam_search_device(step_dev, logits_buf: torch.Tensor, first_logits: torch.T
     ``advance_fn(row_lp, row_tok, st)`` (with ``topk_fn``): the WHOLE bookkeeping of a step as one kernel (`eilev_beam_advance`; st = the
     state tensors below, updated in place, plus the tokens to feed) — the ~35 small torch kernels of `select` cost ~4 us each even inside a
     graph.  ``anc_state`` = (state, tokens): the decode step's device counter (cur = state[0] - 1) and token buffer; `step_dev` is then
-    called with (None, None): the kernel already wrote the tokens and the ancestor table."""
+    called with (None, None): the kernel already wrote the tokens and the ancestor table.
+
+    ``topk_history``: the logits rules that depend on a hypothesis' own ids (`repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens`;
+    `eilev_rules_topk_logprob`, eilev_amd/rules.py) live inside ``topk_fn``, which is then called as ``topk_fn(logits_buf, run_score, run_seq
+    (B, K, T) int64, cur_t)``: row r's history is run_seq[r, 0 .. cur).  cur_t (0-d int64 on the device) counts the selections done when
+    the bookkeeping runs here; with ``advance_fn`` the counter is the caller's (the decode step's state word) and cur_t stays 0."""
     dev = first_logits.device
     B, nb, T = batch, num_beams, max_new_tokens
     V = first_logits.shape[-1]
@@ -88,8 +94,11 @@ def beam_search_device(step_dev, logits_buf: torch.Tensor, first_logits: torch.T
                   can_improve=can_improve, pow_tab=pow_tab, reciprocal=on_gpu, eos=eos, keep=keep,
                   early=1 if early_stopping is True else (2 if (early_stopping == "never" and lp > 0.0) else 0))
 
+    def row_topk():
+        return topk_fn(logits_buf, run_score, run_seq, cur_t) if topk_history else topk_fn(logits_buf, run_score)
+
     def select_fused():
-        row_lp, row_tok = topk_fn(logits_buf, run_score)
+        row_lp, row_tok = row_topk()
         advance_fn(row_lp, row_tok, st)
         flags[0] = can_improve.any()
         flags[1] = finished.all()
@@ -98,7 +107,7 @@ def beam_search_device(step_dev, logits_buf: torch.Tensor, first_logits: torch.T
         if fused:
             return select_fused()
         if topk_fn is not None:
-            row_lp, row_tok = topk_fn(logits_buf, run_score)
+            row_lp, row_tok = row_topk()
             top_lp, pos = torch.topk(row_lp.view(B, nb * keep), keep, dim=1)
             src = pos // keep
             tok = row_tok.view(B, nb * keep).gather(1, pos).to(torch.int64)

@@ -1,5 +1,5 @@
-"""Builds eilev_amd/csrc/libeilev_hip.so and its companions libeilev_hip_pld.so (prompt lookup) and libeilev_hip_sample.so (device
-sampling) (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
+"""Builds eilev_amd/csrc/libeilev_hip.so and its companions libeilev_hip_pld.so (prompt lookup), libeilev_hip_sample.so (device
+sampling) and libeilev_hip_rules.so (logits rules of greedy and beam search) (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
 from __future__ import annotations
 
 import os
@@ -21,6 +21,10 @@ PLD_LIB = os.path.join(HERE, "libeilev_hip_pld.so")
 SAMPLE_SOURCE = "sample.hip"
 SAMPLE_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_sample.h")]
 SAMPLE_LIB = os.path.join(HERE, "libeilev_hip_sample.so")
+# the logits-rules companion (include/eilev_rules.h), built the same way
+RULES_SOURCE = "rules.hip"
+RULES_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_rules.h")]
+RULES_LIB = os.path.join(HERE, "libeilev_hip_rules.so")
 
 
 def _hipcc() -> str:
@@ -65,7 +69,8 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "", ext
 
     # the default build (no variant) also builds the companion libraries; the probe variant does not need them
     side_jobs = []
-    for src, hdr, emap, out in ((PLD_SOURCE, PLD_HEADERS, "exports_pld.map", PLD_LIB), (SAMPLE_SOURCE, SAMPLE_HEADERS, "exports_sample.map", SAMPLE_LIB)):
+    for src, hdr, emap, out in ((PLD_SOURCE, PLD_HEADERS, "exports_pld.map", PLD_LIB), (SAMPLE_SOURCE, SAMPLE_HEADERS, "exports_sample.map", SAMPLE_LIB),
+                                (RULES_SOURCE, RULES_HEADERS, "exports_rules.map", RULES_LIB)):
         src, emap = os.path.join(HERE, src), os.path.join(HERE, emap)
         if not variant and (force or _stale(out, [src, emap] + [os.path.join(HERE, h) for h in hdr])):
             side_jobs.append([_hipcc(), *FLAGS, *extra_flags, "-shared", "-o", out, src, "-Wl,--version-script=" + emap])

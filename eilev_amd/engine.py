@@ -41,6 +41,8 @@ class HipEngine:
         self._dec_cache = None  # most recent captured decode step + the buffers it is bound to
         self.device_sampling = True  # generate(do_sample=True, num_beams=1): the draw runs in the captured step (sample_decode_device); False: the host loop
         self.sample_stats = None     # per sampling call: dict(path="device" | "host", steps=generated tokens per row)
+        self.device_rules = True     # greedy / beam search with repetition_penalty, no_repeat_ngram_size, min_new_tokens or several EOS ids: the
+        self.rules_stats = None      # rules run in the captured step (include/eilev_rules.h); per such call: dict(path="device" | "host", steps=)
         self.parts = tuple(parts)
         if lm_weights not in ("bf16", "fp8", "fp8_mfma"):
             raise ValueError("lm_weights must be 'bf16', 'fp8' (e4m3 weights, bf16 activations) or 'fp8_mfma' (e4m3 weights AND per-token "
@@ -805,7 +807,9 @@ class HipEngine:
                     early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, use_graph=True, trace=None, rules=None):
         """Beam search on the HIP path [sample default: num_beams=5, length_penalty=-1; hf generation/utils.py:3208+].
         ``trace``: a list that receives (tokens fed, parent rows, fp32 logits) of every step (tests replay the hypotheses teacher-forced).
-        ``rules``: dict(processors=, stopping=, prefix=) for the host loops (eilev_amd/sampling.py, beam.py): hf logits processors / stopping criteria.
+        ``rules``: dict(processors=, stopping=, prefix=) for the host loops (eilev_amd/sampling.py, beam.py): hf logits processors / stopping criteria;
+        and the numbers repetition_penalty= / no_repeat_ngram_size=, which — like min_new_tokens and several EOS ids — run on the device in the
+        step when `_route_rules` says so (``self.rules_stats`` says which path ran), else as transformers' processors in the host loops.
 
         The prompt is prefilled ONCE per sample; no cache row is ever copied (see below); one HIP decode step on all rows per
         generated token, captured into a hipGraph and replayed."""
@@ -816,10 +820,24 @@ class HipEngine:
         R = B * num_beams
         if num_beams > 32:
             raise NotImplementedError("num_beams > 32")
-        if sampler is not None and num_beams == 1:
+        from .sampling import eos_list
+
+        rules_kw, with_rules, rules_in = None, False, rules
+        if sampler is not None and num_beams == 1 and not sampler.get("greedy"):
             sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id, trace)
             if dev_kw is not None:
                 return self.sample_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, **dev_kw)
+        else:
+            # greedy search (num_beams == 1, sampler = dict(greedy=True)) and beam search: the rules run on the device when the route says so and,
+            # for beams, when the search takes the fused topk_fn + advance_fn form below; beam-search sampling keeps the host loop
+            keep = max(2, 1 + len(eos_list(eos_id))) * num_beams
+            fused_ok = (sampler is None and num_beams > 1 and getattr(self, "beam_device_loop", True) and getattr(self, "beam_topk_kernel", True) and
+                        getattr(self, "beam_advance_kernel", True) and keep <= abi.RULES_MAX_KEEP and num_beams * keep <= 2048 and
+                        max(1, max_new_tokens) * num_beams <= 2048)
+            min_new = int(min_new_tokens) if sampler is None else int(sampler.get("min_new_tokens", 0) or 0)
+            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, trace, allow_device=fused_ok or (sampler is not None and num_beams == 1))
+            if rules_kw is not None and num_beams == 1:
+                return self.rules_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, **rules_kw)
         if R > 32:
             # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are
             # independent in beam search); shorter results are padded with pad_id like HF pads finished hypotheses
@@ -828,6 +846,8 @@ class HipEngine:
                 raise ValueError("trace: at most 32 decode rows")
             if rules and rules.get("prefix") is not None:
                 raise NotImplementedError("prefix ids with more than 32 decode rows")
+            if rules_kw is not None or with_rules:  # (every part is routed again: it gets the caller's rules, numbers included)
+                rules = rules_in
             parts = [self.beam_decode(inputs_embeds[i:i + per], attention_mask[i:i + per], max_new_tokens, num_beams, length_penalty, eos_id,
                                       pad_id, early_stopping, num_return_sequences, sampler, min_new_tokens, use_graph, None, rules) for i in range(0, B, per)]
             n = max(p.shape[1] for p in parts)
@@ -887,7 +907,8 @@ class HipEngine:
                 trace.append((next_tokens.clone(), beam_src.clone(), logits.clone()))
             return logits
 
-        if sampler is None and not rules and int(min_new_tokens) == 0 and trace is None and num_beams > 1 and getattr(self, "beam_device_loop", True):
+        if sampler is None and (rules_kw is not None or (not rules and int(min_new_tokens) == 0)) and trace is None and num_beams > 1 and \
+                getattr(self, "beam_device_loop", True):
             # (r4) plain beam search — the sample script's call: selection, ancestor-table update and the decode step as ONE captured graph per
             # generated token, nothing indexed by the step on the host (eilev_amd/beam.py::beam_search_device)
             from .beam import beam_search_device
@@ -902,8 +923,6 @@ class HipEngine:
                 tokens.copy_(next_tokens)
                 launch()
                 tpos.add_(1)
-
-            from .sampling import eos_list
 
             keep = max(2, 1 + len(eos_list(eos_id))) * num_beams
             topk_fn = None
@@ -937,20 +956,39 @@ class HipEngine:
             # token (2.565 vs 2.554 ms) and costs ~1.2 ms per generate() call — replayed graphs only on request (`engine.beam_capture = True`)
             # or when the selection runs as torch ops
             capture = use_graph and (advance_fn is None or getattr(self, "beam_capture", False))
+            if rules_kw is not None:
+                # the rules of the call inside the per-row selection (eilev_rules_topk_logprob): row r's history is run_seq[r, 0 .. cur), which
+                # eilev_beam_advance keeps in place, and cur = state[0] - 1 is the decode step's device counter
+                assert advance_fn is not None, "the route checked the conditions of the fused form"
+                rl = abi.load_rules()
+                p_rules = abi.rules_params(rules_kw["repetition_penalty"], rules_kw["no_repeat_ngram_size"], rules_kw["min_new_tokens"], max_new_tokens,
+                                           eos_list(eos_id), pad_id, -1, 0, 0)
+
+                def topk_fn(buf, run_score, run_seq, cur_t):  # noqa: F811
+                    abi.check(rl.eilev_rules_topk_logprob(C.byref(p_rules), _ptr(buf), _ptr(run_score), R, d.vocab, keep, _ptr(state), _ptr(run_seq),
+                                                          _ptr(row_lp), _ptr(row_tok), None, None, 0, self._stream()), "eilev_rules_topk_logprob")
+                    return row_lp, row_tok
+
             out = beam_search_device(step_dev, logits, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
-                                     num_return_sequences, use_graph=capture, topk_fn=topk_fn, advance_fn=advance_fn)
+                                     num_return_sequences, use_graph=capture, topk_fn=topk_fn, advance_fn=advance_fn, topk_history=rules_kw is not None)
             self._decode_warm = True
+            if rules_kw is not None:
+                self.rules_stats = dict(path="device", steps=int(out.shape[1]))
             return out
         if sampler is not None and num_beams == 1:  # multinomial sampling: eilev_amd/sampling.py on the same decode step
             from .sampling import sample_loop
 
             ids = sample_loop(step, last, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
             self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
+            if with_rules:
+                self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
             return ids
         ids = beam_search(step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
                           num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
         if sampler is not None:  # beam-search sampling
             self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
+        elif with_rules:
+            self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
         return ids
 
     def sample_decode(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
@@ -964,23 +1002,62 @@ class HipEngine:
     def _route_sampling(self, sampler, rules, vocab, eos_id, trace=None):
         """Where a `sampler is not None and num_beams == 1` call runs.  Returns (sampler, rules, dev_kw): dev_kw is the keyword set of
         sample_decode_device / t5_sample_device when the device path takes the call, else None with (sampler, rules) in the form the host
-        loop (eilev_amd/sampling.py sample_loop) takes — a numeric repetition_penalty becomes transformers' processor again."""
+        loop (eilev_amd/sampling.py sample_loop) takes — a numeric repetition_penalty / no_repeat_ngram_size becomes transformers' processor
+        again."""
         from .sampling import eos_list
 
         sampler = dict(sampler)
         pen = float(sampler.pop("repetition_penalty", None) or 1.0)
+        ngram = int(sampler.pop("no_repeat_ngram_size", None) or 0)
         host_only = bool(rules) and (rules.get("processors") is not None or rules.get("stopping") is not None)
         if (getattr(self, "device_sampling", True) and not host_only and trace is None and not sampler.get("greedy") and
-                len(eos_list(eos_id)) <= abi.SAMPLE_MAX_EOS and abi.sample_supported(vocab)):
-            return sampler, rules, dict(temperature=sampler.get("temperature", 1.0), top_k=sampler.get("top_k", 50), top_p=sampler.get("top_p", 1.0),
-                                        repetition_penalty=pen, min_new_tokens=sampler.get("min_new_tokens", 0), generator=sampler.get("generator"))
-        if pen != 1.0:
-            from transformers import LogitsProcessorList, RepetitionPenaltyLogitsProcessor
-
+                len(eos_list(eos_id)) <= abi.SAMPLE_MAX_EOS and abi.sample_supported(vocab) and (not ngram or abi.rules_supported(vocab))):
+            dev_kw = dict(temperature=sampler.get("temperature", 1.0), top_k=sampler.get("top_k", 50), top_p=sampler.get("top_p", 1.0),
+                          repetition_penalty=pen, min_new_tokens=sampler.get("min_new_tokens", 0), generator=sampler.get("generator"))
+            if ngram:
+                dev_kw["no_repeat_ngram_size"] = ngram
+            return sampler, rules, dev_kw
+        if pen != 1.0 or ngram:
             rules = dict(rules or {})
-            rules["processors"] = LogitsProcessorList([RepetitionPenaltyLogitsProcessor(penalty=pen)] + list(rules.get("processors") or []))
+            rules["processors"] = self._host_processors(pen, ngram, rules.get("processors"))
             rules.setdefault("stopping", None)
         return sampler, rules, None
+
+    @staticmethod
+    def _host_processors(pen, ngram, more=None):
+        """The numeric rules as transformers' own processors, in hf's order, in front of the caller's."""
+        from transformers import LogitsProcessorList, NoRepeatNGramLogitsProcessor, RepetitionPenaltyLogitsProcessor
+
+        lst = LogitsProcessorList()
+        if pen != 1.0:
+            lst.append(RepetitionPenaltyLogitsProcessor(penalty=pen))
+        if ngram:
+            lst.append(NoRepeatNGramLogitsProcessor(ngram))
+        lst.extend(list(more or []))
+        return lst
+
+    def _route_rules(self, rules, vocab, eos_id, min_new_tokens=0, trace=None, allow_device=True):
+        """Where a greedy or beam search call with rules runs.  ``rules`` may carry the numbers ``repetition_penalty`` and
+        ``no_repeat_ngram_size`` beside processors= / stopping= / prefix= / fill_id=.  Returns (dev_kw, rules, with_rules): dev_kw is the
+        keyword set of the device path (rules_decode_device, t5_rules_device, the eilev_rules_topk_logprob closure of beam_decode) when it
+        takes the call — no user processor, no stopping criterion, no trace, at most 8 EOS ids, a vocabulary the library takes — else None
+        with ``rules`` in the form the host loops take: the numbers as transformers' processors again.  with_rules: the call carries any
+        rule at all (a plain call is not routed and leaves rules_stats alone)."""
+        from .sampling import eos_list
+
+        rules = dict(rules or {})
+        pen = float(rules.pop("repetition_penalty", None) or 1.0)
+        ngram = int(rules.pop("no_repeat_ngram_size", None) or 0)
+        host_only = rules.get("processors") is not None or rules.get("stopping") is not None
+        n_eos = len(eos_list(eos_id))
+        with_rules = pen != 1.0 or ngram > 0 or int(min_new_tokens) > 0 or n_eos > 1 or host_only
+        if (with_rules and allow_device and getattr(self, "device_rules", True) and not host_only and trace is None and
+                n_eos <= abi.RULES_MAX_EOS and abi.rules_supported(vocab)):
+            return dict(repetition_penalty=pen, no_repeat_ngram_size=ngram, min_new_tokens=int(min_new_tokens)), (rules or None), True
+        if pen != 1.0 or ngram:
+            rules["processors"] = self._host_processors(pen, ngram, rules.get("processors"))
+            rules.setdefault("stopping", None)
+        return None, (rules or None), with_rules
 
     def _sample_setup(self, R, vocab, max_new_tokens, generator, uniforms, **spec):
         """The sampling library, the uniforms of a whole call — (max_new, R), drawn ONCE on the generator's device — and a function that makes
@@ -1003,6 +1080,24 @@ class HipEngine:
         abi.check(smp.eilev_sample_select(C.byref(params), _ptr(logits), R, vocab, _ptr(uni), _ptr(state), _ptr(finished), _ptr(tokens), _ptr(out),
                                           _ptr(warped) if warped is not None else None, _ptr(scratch) if scratch.numel() else None, scratch.numel(),
                                           self._stream()), "eilev_sample_select")
+
+    def _rules_setup(self, vocab, max_new_tokens, **spec):
+        """The rules library and a function that makes the parameter block of one of its calls."""
+        rl = abi.load_rules()
+        if not abi.rules_supported(vocab):
+            raise NotImplementedError(f"device rules: vocab {vocab} (at most {abi.RULES_MAX_VOCAB}, a multiple of 4)")
+
+        def params(step_offset, finalize):
+            return abi.rules_params(max_new=max_new_tokens, step_offset=step_offset, finalize=finalize, **spec)
+
+        return rl, params
+
+    def _rules_select(self, rl, params, logits, R, vocab, state, finished, tokens, out):
+        abi.check(rl.eilev_rules_select(C.byref(params), _ptr(logits), R, vocab, _ptr(state), _ptr(finished), _ptr(tokens), _ptr(out), None, None, 0,
+                                        self._stream()), "eilev_rules_select")
+
+    def _rules_ban(self, rl, params, logits, R, vocab, state, out):
+        abi.check(rl.eilev_rules_ban(C.byref(params), _ptr(logits), R, vocab, _ptr(state), _ptr(out), self._stream()), "eilev_rules_ban")
 
     def _trim_sampled(self, out, n, eos, pad_id):
         """The first n columns of `out`, cut where every row has drawn an EOS id (hf stops there); finished rows already hold the pad id."""
@@ -1046,43 +1141,35 @@ class HipEngine:
                 break
         return done
 
-    def sample_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
-                             repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None):
-        """Multinomial sampling with the draw on the device (include/eilev_sample.h): greedy_decode's structure — one KV cache of capacity
-        L + max_new, the stream layout, ONE captured step replayed per token — with eilev_sample_select after the decode step.  The decode
-        step's own arg-max writes to scratch buffers (eos -1); eilev_sample_select then overwrites `tokens`.  ``eos_id``: an id or up to 8 ids.
-        ``trace``: a list that receives a copy of every step's logits (use_graph=False).  ``uniforms``: (max_new, rows) in [0, 1) instead of
-        the ones drawn from ``generator``.  Returns int64 (B, n) new tokens."""
-        from .sampling import eos_list
+    def _chunked_rows(self, call, B, stats_name, pad_id):
+        """More than 32 rows: ``call(i, j)`` on consecutive 32-row slices (as greedy_decode), shorter parts padded like hf pads rows that
+        stopped early; the stats record of the whole call holds the longest part's steps."""
+        parts, n_steps = [], 0
+        for i in range(0, B, 32):
+            parts.append(call(i, min(i + 32, B)))
+            n_steps = max(n_steps, getattr(self, stats_name)["steps"])
+        n = max(p.shape[1] for p in parts)
+        setattr(self, stats_name, dict(path="device", steps=n_steps))
+        return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
 
+    def _select_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace):
+        """greedy_decode's structure — one KV cache of capacity L + max_new, the stream layout, ONE captured step replayed per token — with a
+        selection of the caller's after the decode step (the draw of sample_decode_device, the rules + arg-max of rules_decode_device).  The
+        decode step's own arg-max writes to scratch buffers (eos -1); the selection then overwrites `tokens`.
+
+        ``key``: what the captured step depends on beside the shape (the parameter block is passed by value): one cached entry, in
+        greedy_decode's slot (a call of the other kind replaces it, so one KV cache is kept at a time).  ``extra(B)``: the selection's own
+        buffers of a new entry.  ``bind(ent) -> (first(logits), step(logits))``: called once per call with the entry's buffers; `first` selects
+        from the prefill's logits (state[0] = 0, it finalizes the step itself), `step` from the decode step's (which has already advanced
+        state[0]).  At most 32 rows.  Returns int64 (B, n) new tokens."""
         d = self.dims
         B, L, _ = inputs_embeds.shape
-        if max_new_tokens <= 0:
-            return torch.empty((B, 0), dtype=torch.int64, device=self.device)
-        eos = eos_list(eos_id)
-        spec = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos,
-                    pad_id=pad_id, prefix_id=-1)
-        smp, uni_all, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, **spec)
-        if B > 32:  # as greedy_decode: consecutive 32-row decodes, shorter parts padded like hf pads rows that stopped early
-            if trace is not None:
-                raise ValueError("trace: at most 32 decode rows")
-            parts, n_steps = [], 0
-            for i in range(0, B, 32):
-                parts.append(self.sample_decode_device(inputs_embeds[i:i + 32], attention_mask[i:i + 32], max_new_tokens, eos_id, pad_id, temperature, top_k,
-                                                       top_p, repetition_penalty, min_new_tokens, None, use_graph, poll_every, None, uni_all[:, i:i + 32]))
-                n_steps = max(n_steps, self.sample_stats["steps"])
-            n = max(p.shape[1] for p in parts)
-            self.sample_stats = dict(path="device", steps=n_steps)
-            return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
         cap = L + max_new_tokens
         n_dec = max_new_tokens - 1
         if n_dec > 0:
             self.ensure_stream_layout(B)
         graphable = use_graph and n_dec > 1 and trace is None
-        # the captured step depends on buffer addresses, on the shape and on the parameter block (passed by value): one cached entry, in
-        # greedy_decode's slot (a call of the other kind replaces it, so one KV cache is kept at a time)
-        key = ("sample", B, L, cap, max_new_tokens, float(temperature), int(top_k or 0), float(top_p), float(repetition_penalty), int(min_new_tokens),
-               tuple(eos), int(pad_id))
+        key = tuple(key) + (B, L, cap, max_new_tokens, tuple(eos), int(pad_id))
         ent = self._dec_cache if (graphable and self._dec_cache is not None and self._dec_cache["key"] == key) else None
         if ent is None:
             ent = dict(key=key, graph=None,
@@ -1093,23 +1180,21 @@ class HipEngine:
                        finished=torch.zeros(B, dtype=torch.uint8, device=self.device),
                        tokens=torch.zeros(B, dtype=torch.int64, device=self.device),
                        out=torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device),
-                       uni=torch.empty((max_new_tokens, B), dtype=torch.float32, device=self.device),
                        argmax_out=torch.zeros((B, max_new_tokens), dtype=torch.int64, device=self.device),   # the decode step's own selection:
                        argmax_fin=torch.zeros(B, dtype=torch.uint8, device=self.device),                     # never read
-                       scratch=torch.empty(int(smp.eilev_sample_scratch_bytes(B, d.vocab)), dtype=torch.uint8, device=self.device),
                        logits=torch.empty((B, d.vocab), dtype=torch.float32, device=self.device),
-                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1)))
+                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1)), **extra(B))
             if graphable:
                 self._dec_cache = None  # drop the previous entry (its KV cache) before keeping this one
                 self._dec_cache = ent
-        am, n_valid, kv, uni, scratch = ent["am"], ent["n_valid"], ent["kv"], ent["uni"], ent["scratch"]
+        am, n_valid, kv = ent["am"], ent["n_valid"], ent["kv"]
         state, finished, tokens, out, logits, ws = ent["state"], ent["finished"], ent["tokens"], ent["out"], ent["logits"], ent["ws"]
         am.copy_(attention_mask.to(self.device, torch.int32))
         n_valid.copy_(am.sum(dim=1))
-        uni.copy_(uni_all)
         state.zero_()
         finished.zero_()
         out.fill_(int(pad_id))
+        first, step = bind(ent)
         last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
         if self.timing is not None:  # optional phase stamps for bench.py (events on the launch stream, no sync)
             ev = torch.cuda.Event(enable_timing=True)
@@ -1117,51 +1202,109 @@ class HipEngine:
             self.timing.append(("prefill_done", ev))
         if trace is not None:
             trace.append(last.clone())
-        self._sample_select(smp, params(0, 1), last, B, d.vocab, uni, state, finished, tokens, out, scratch)
-        p_step = params(-1, 0)  # (the decode step has already advanced state[0])
+        first(last)
 
         def one_step():
             abi.check(self.lib.eilev_opt_decode_step(
                 C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), B, L, _ptr(kv), cap,
                 _ptr(logits), _ptr(ent["argmax_fin"]), -1, pad_id, _ptr(ent["argmax_out"]), max_new_tokens, _ptr(ws), ws.numel(),
                 self._stream()), "eilev_opt_decode_step")
-            self._sample_select(smp, p_step, logits, B, d.vocab, uni, state, finished, tokens, out, scratch)
+            step(logits)
 
         graph = ent["graph"] if graphable else None
         if graphable and graph is None:  # (once per engine the step also runs outside capture: lazy module loading of the kernels)
             graph = ent["graph"] = self._capture_sample_step(one_step, (state, finished, tokens, out), warm=not self._decode_warm)
             self._decode_warm = True
         done_steps = self._run_sample_steps(n_dec, one_step, graph, state, eos, poll_every, trace, logits)
-        ids = self._trim_sampled(out, 1 + done_steps, eos, pad_id)
+        return self._trim_sampled(out, 1 + done_steps, eos, pad_id)
+
+    def sample_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
+                             repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None,
+                             no_repeat_ngram_size=0):
+        """Multinomial sampling with the draw on the device (include/eilev_sample.h): _select_decode_device with eilev_sample_select after the
+        decode step, and eilev_rules_ban in front of it for ``no_repeat_ngram_size`` (hf applies the ban before the warpers).  ``eos_id``: an
+        id or up to 8 ids.  ``trace``: a list that receives a copy of every step's logits (use_graph=False; the n-gram ban is already written into them).  ``uniforms``:
+        (max_new, rows) in [0, 1) instead of the ones drawn from ``generator``.  Returns int64 (B, n) new tokens."""
+        from .sampling import eos_list
+
+        d = self.dims
+        B = inputs_embeds.shape[0]
+        if max_new_tokens <= 0:
+            return torch.empty((B, 0), dtype=torch.int64, device=self.device)
+        eos = eos_list(eos_id)
+        ngram = int(no_repeat_ngram_size or 0)
+        spec = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos,
+                    pad_id=pad_id, prefix_id=-1)
+        smp, uni_all, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, **spec)
+        if B > 32:
+            if trace is not None:
+                raise ValueError("trace: at most 32 decode rows")
+            return self._chunked_rows(lambda i, j: self.sample_decode_device(
+                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, temperature, top_k, top_p, repetition_penalty, min_new_tokens,
+                None, use_graph, poll_every, None, uni_all[:, i:j], ngram), B, "sample_stats", pad_id)
+        rl, ban_params = self._rules_setup(d.vocab, max_new_tokens, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id) if ngram else (None, None)
+
+        def extra(rows):
+            return dict(uni=torch.empty((max_new_tokens, rows), dtype=torch.float32, device=self.device),
+                        scratch=torch.empty(int(smp.eilev_sample_scratch_bytes(rows, d.vocab)), dtype=torch.uint8, device=self.device))
+
+        def bind(ent):
+            state, finished, tokens, out, uni, scratch = ent["state"], ent["finished"], ent["tokens"], ent["out"], ent["uni"], ent["scratch"]
+            uni.copy_(uni_all)
+
+            def select(p_ban, p_draw):
+                def fn(lg):
+                    if ngram:
+                        self._rules_ban(rl, p_ban, lg, B, d.vocab, state, out)
+                    self._sample_select(smp, p_draw, lg, B, d.vocab, uni, state, finished, tokens, out, scratch)
+                return fn
+
+            # (the decode step has already advanced state[0]: step_offset -1, no finalize)
+            return select(ban_params(0, 0) if ngram else None, params(0, 1)), select(ban_params(-1, 0) if ngram else None, params(-1, 0))
+
+        key = ("sample", float(temperature), int(top_k or 0), float(top_p), float(repetition_penalty), int(min_new_tokens), ngram)
+        ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace)
         self.sample_stats = dict(path="device", steps=int(ids.shape[1]))
         return ids
 
-    def t5_sample_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, temperature=1.0, top_k=50, top_p=1.0,
-                         repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None):
-        """t5_greedy with eilev_sample_select in place of the arg-max: decoder ids (B, 1 + n) INCLUDING the start token, which the repetition
-        penalty sees (prefix_id), as hf's processors do.  ``trace`` / ``uniforms``: as sample_decode_device."""
+    def rules_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                            min_new_tokens=0, use_graph=True, poll_every=8, trace=None):
+        """Greedy search with logits rules on the device (include/eilev_rules.h): _select_decode_device with eilev_rules_select — repetition
+        penalty, n-gram ban, minimum length, up to 8 EOS ids, then the arg-max — after the decode step.  ``trace``: a list that receives a
+        copy of every step's logits (use_graph=False).  Returns int64 (B, n) new tokens."""
         from .sampling import eos_list
 
-        d = self.t5dims
+        d = self.dims
         B = inputs_embeds.shape[0]
-        start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
         if max_new_tokens <= 0:
-            return start
+            return torch.empty((B, 0), dtype=torch.int64, device=self.device)
         eos = eos_list(eos_id)
-        smp, uni, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, temperature=temperature, top_k=top_k, top_p=top_p,
-                                              repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos, pad_id=pad_id,
-                                              prefix_id=int(start_id))
-        if B > 32:  # as sample_decode_device: consecutive 32-row decodes on slices of the same uniforms, shorter parts padded
+        ngram = int(no_repeat_ngram_size or 0)
+        rl, params = self._rules_setup(d.vocab, max_new_tokens, repetition_penalty=repetition_penalty, no_repeat_ngram=ngram, min_new=min_new_tokens,
+                                       eos_ids=eos, pad_id=pad_id, prefix_id=-1)
+        if B > 32:
             if trace is not None:
                 raise ValueError("trace: at most 32 decode rows")
-            parts, n_steps = [], 0
-            for i in range(0, B, 32):
-                parts.append(self.t5_sample_device(inputs_embeds[i:i + 32], attention_mask[i:i + 32], max_new_tokens, eos_id, pad_id, start_id, temperature,
-                                                   top_k, top_p, repetition_penalty, min_new_tokens, None, use_graph, poll_every, None, uni[:, i:i + 32]))
-                n_steps = max(n_steps, self.sample_stats["steps"])
-            n = max(p.shape[1] for p in parts)
-            self.sample_stats = dict(path="device", steps=n_steps)
-            return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
+            return self._chunked_rows(lambda i, j: self.rules_decode_device(
+                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, repetition_penalty, ngram, min_new_tokens, use_graph, poll_every),
+                B, "rules_stats", pad_id)
+
+        def bind(ent):
+            def select(p):
+                return lambda lg: self._rules_select(rl, p, lg, B, d.vocab, ent["state"], ent["finished"], ent["tokens"], ent["out"])
+            return select(params(0, 1)), select(params(-1, 0))
+
+        key = ("rules", float(repetition_penalty), ngram, int(min_new_tokens))
+        ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, lambda rows: {}, bind, use_graph, poll_every,
+                                         trace)
+        self.rules_stats = dict(path="device", steps=int(ids.shape[1]))
+        return ids
+
+    def _t5_select_device(self, inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id, bind, use_graph, poll_every, trace):
+        """t5_greedy's structure with a selection of the caller's in place of eilev_greedy_select: ``bind(state, finished, tokens, out) ->
+        step(logits)``.  At most 32 rows.  Returns the new ids (B, n), without the start token."""
+        d = self.t5dims
+        B = inputs_embeds.shape[0]
         enc = self.t5_encode(inputs_embeds, attention_mask)
         ckv = self.t5_cross_kv(enc)
         L = enc.shape[1]
@@ -1173,21 +1316,89 @@ class HipEngine:
         tokens = torch.full((B,), int(start_id), dtype=torch.int64, device=self.device)
         out = torch.full((B, max_new_tokens), int(pad_id), dtype=torch.int64, device=self.device)
         logits = torch.empty((B, d.vocab), dtype=torch.float32, device=self.device)
-        scratch = torch.empty(int(smp.eilev_sample_scratch_bytes(B, d.vocab)), dtype=torch.uint8, device=self.device)
         ws = self._workspace("t5dec", self.lib.eilev_t5_workspace_bytes(C.byref(d), B, 1, max(L, cap)))
-        p_step = params(0, 1)
+        step = bind(state, finished, tokens, out)
 
         def one_step():
             abi.check(self.lib.eilev_t5_decode_step(C.byref(d), C.byref(self.pack.t5), _ptr(tokens), _ptr(state), _ptr(am), B, _ptr(skv), cap,
                                                     _ptr(ckv), L, _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_t5_decode_step")
-            self._sample_select(smp, p_step, logits, B, d.vocab, uni, state, finished, tokens, out, scratch)
+            step(logits)
 
         graph = None
         if use_graph and max_new_tokens > 1 and trace is None:  # (the warm-up step only touches cache slot 0, which the replay rewrites)
             graph = self._capture_sample_step(one_step, (state, finished, tokens, out), warm=True)
         n = self._run_sample_steps(max_new_tokens, one_step, graph, state, eos, poll_every, trace, logits, poll_last=True)
-        ids = self._trim_sampled(out, n, eos, pad_id)
+        return self._trim_sampled(out, n, eos, pad_id)
+
+    def t5_sample_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, temperature=1.0, top_k=50, top_p=1.0,
+                         repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None,
+                         no_repeat_ngram_size=0):
+        """t5_greedy with eilev_sample_select in place of the arg-max (and eilev_rules_ban in front of it for ``no_repeat_ngram_size``):
+        decoder ids (B, 1 + n) INCLUDING the start token, which the rules see (prefix_id), as hf's processors do.  ``trace`` / ``uniforms``:
+        as sample_decode_device."""
+        from .sampling import eos_list
+
+        d = self.t5dims
+        B = inputs_embeds.shape[0]
+        start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
+        if max_new_tokens <= 0:
+            return start
+        eos = eos_list(eos_id)
+        ngram = int(no_repeat_ngram_size or 0)
+        smp, uni, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, temperature=temperature, top_k=top_k, top_p=top_p,
+                                              repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos, pad_id=pad_id,
+                                              prefix_id=int(start_id))
+        if B > 32:
+            if trace is not None:
+                raise ValueError("trace: at most 32 decode rows")
+            ids = self._chunked_rows(lambda i, j: self.t5_sample_device(
+                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, start_id, temperature, top_k, top_p, repetition_penalty,
+                min_new_tokens, None, use_graph, poll_every, None, uni[:, i:j], ngram)[:, 1:], B, "sample_stats", pad_id)
+            return torch.cat((start, ids), dim=1)
+        rl, ban_params = self._rules_setup(d.vocab, max_new_tokens, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id,
+                                           prefix_id=int(start_id)) if ngram else (None, None)
+        scratch = torch.empty(int(smp.eilev_sample_scratch_bytes(B, d.vocab)), dtype=torch.uint8, device=self.device)
+        p_step, p_ban = params(0, 1), (ban_params(0, 0) if ngram else None)
+
+        def bind(state, finished, tokens, out):
+            def step(lg):
+                if ngram:
+                    self._rules_ban(rl, p_ban, lg, B, d.vocab, state, out)
+                self._sample_select(smp, p_step, lg, B, d.vocab, uni, state, finished, tokens, out, scratch)
+            return step
+
+        ids = self._t5_select_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id, bind, use_graph, poll_every, trace)
         self.sample_stats = dict(path="device", steps=int(ids.shape[1]))
+        return torch.cat((start, ids), dim=1)
+
+    def t5_rules_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, repetition_penalty=1.0,
+                        no_repeat_ngram_size=0, min_new_tokens=0, use_graph=True, poll_every=8, trace=None):
+        """t5_greedy with eilev_rules_select in place of eilev_greedy_select: decoder ids (B, 1 + n) INCLUDING the start token, which the
+        rules see (prefix_id), as hf's processors do.  ``trace``: as rules_decode_device."""
+        from .sampling import eos_list
+
+        d = self.t5dims
+        B = inputs_embeds.shape[0]
+        start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
+        if max_new_tokens <= 0:
+            return start
+        eos = eos_list(eos_id)
+        ngram = int(no_repeat_ngram_size or 0)
+        rl, params = self._rules_setup(d.vocab, max_new_tokens, repetition_penalty=repetition_penalty, no_repeat_ngram=ngram, min_new=min_new_tokens,
+                                       eos_ids=eos, pad_id=pad_id, prefix_id=int(start_id))
+        if B > 32:
+            if trace is not None:
+                raise ValueError("trace: at most 32 decode rows")
+            ids = self._chunked_rows(lambda i, j: self.t5_rules_device(
+                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, start_id, repetition_penalty, ngram, min_new_tokens, use_graph,
+                poll_every)[:, 1:], B, "rules_stats", pad_id)
+            return torch.cat((start, ids), dim=1)
+        p_step = params(0, 1)
+        ids = self._t5_select_device(
+            inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id,
+            lambda state, finished, tokens, out: (lambda lg: self._rules_select(rl, p_step, lg, B, d.vocab, state, finished, tokens, out)),
+            use_graph, poll_every, trace)
+        self.rules_stats = dict(path="device", steps=int(ids.shape[1]))
         return torch.cat((start, ids), dim=1)
 
 
@@ -1397,8 +1608,19 @@ class HipEngine:
             e = eos_list(eos_id)
             pad_id = e[0] if e else -1
         d = self.t5dims
+        with_rules = False
+        if sampler is None or sampler.get("greedy") or num_beams > 1:
+            # greedy search with rules runs on the device (t5_rules_device); beam search has no device loop for this model: its rules, numbers
+            # included, run in the host loop
+            greedy1 = sampler is not None and num_beams == 1
+            min_new = int(sampler.get("min_new_tokens", 0) or 0) if sampler is not None else int(min_new_tokens)
+            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, allow_device=greedy1)
+            if rules_kw is not None:
+                return self.t5_rules_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, start_id=start_id, **rules_kw)
         if sampler is not None and num_beams == 1:
-            sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id)
+            dev_kw = None
+            if not sampler.get("greedy"):
+                sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id)
             if dev_kw is not None:
                 return self.t5_sample_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, start_id=start_id, **dev_kw)
             if rules and rules.get("processors") is not None and rules.get("prefix") is None:  # hf's processors see the start token
@@ -1427,11 +1649,15 @@ class HipEngine:
 
             ids = sample_loop(step, first, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
             self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
+            if with_rules:
+                self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
         else:
             ids = beam_search(step, first[::num_beams].contiguous(), B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id,
                               early_stopping, num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
             if sampler is not None:  # beam-search sampling
                 self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
+            elif with_rules:
+                self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
         head = torch.full((ids.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
         return torch.cat((head, ids), dim=1)
 

@@ -9,7 +9,9 @@ state-dict names; none of them has arithmetic in its ``forward``
 ``forward`` or ``generate`` on a model that is not on an AMD GPU raises.
 
 Not built (raise ``NotImplementedError``): contrastive / group-beam decoding (greedy, multinomial sampling, beam search and beam-search sampling
-are).  ``output_hidden_states`` / ``output_attentions`` inside the full model's ``forward`` are served from slow paths for the vision wrapper,
+are).  ``generate`` takes ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_new_tokens`` and several EOS ids as numbers: greedy search, sampling and (OPT)
+beam search apply them on the device in the captured decode step; user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
+``output_hidden_states`` / ``output_attentions`` inside the full model's ``forward`` are served from slow paths for the vision wrapper,
 the Q-Former (self- and cross-attention weights), the OPT language model and the T5 stacks (hidden states; self- and cross-attention weights).  ``decoder_attention_mask`` with padding is honoured on the evaluation route (the first target position of a row must stay visible).
 """
 from __future__ import annotations
@@ -545,8 +547,8 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         # like hf, output_scores / output_logits without return_dict_in_generate change nothing.
         want_dict = bool(kw.pop("return_dict_in_generate", False))
         want_scores, want_logits = bool(kw.pop("output_scores", False)) and want_dict, bool(kw.pop("output_logits", False)) and want_dict
-        # hf hands every other kwarg to GenerationMixin (ref:eilev/model/v2.py:318-322).  Logits processors and stopping criteria run in the
-        # host loops over the same HIP decode step, with transformers' own processor classes (exactly hf's arithmetic and order).
+        # hf hands every other kwarg to GenerationMixin (ref:eilev/model/v2.py:318-322).  User logits processors and stopping criteria run in
+        # the host loops over the same HIP decode step, with transformers' own processor classes (exactly hf's arithmetic and order).
         from transformers import (LogitsProcessorList, MaxTimeCriteria, NoRepeatNGramLogitsProcessor, RepetitionPenaltyLogitsProcessor,
                                   StoppingCriteriaList)
 
@@ -554,24 +556,30 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         rp = kw.pop("repetition_penalty", None)
         ngram = kw.pop("no_repeat_ngram_size", None)
         user_procs = kw.pop("logits_processor", None)
-        if rp is not None and float(rp) != 1.0:
-            if sampler is not None and num_beams == 1 and not ngram and not user_procs:
-                # the only processor of a sampling call: the engine takes it as a number — the device path applies it in the captured step
-                # (include/eilev_sample.h), the host loop wraps it into the same transformers processor (engine._route_sampling)
-                sampler["repetition_penalty"] = float(rp)
-            else:
-                procs.append(RepetitionPenaltyLogitsProcessor(penalty=float(rp)))
-        if ngram:
-            procs.append(NoRepeatNGramLogitsProcessor(int(ngram)))
-        if user_procs:
+        rp = float(rp) if rp is not None and float(rp) != 1.0 else None
+        ngram = int(ngram) if ngram else None
+        numbers = {}
+        if not user_procs:
+            # the only processors of the call: the engine takes them as numbers — the device paths apply them in the captured step
+            # (include/eilev_sample.h, include/eilev_rules.h), the host loops wrap them into the same transformers processors again
+            # (engine._route_sampling, engine._route_rules)
+            numbers = {k: v for k, v in (("repetition_penalty", rp), ("no_repeat_ngram_size", ngram)) if v is not None}
+            if sampler is not None and num_beams == 1:
+                sampler.update(numbers)
+                numbers = {}
+        else:
+            if rp is not None:
+                procs.append(RepetitionPenaltyLogitsProcessor(penalty=rp))
+            if ngram:
+                procs.append(NoRepeatNGramLogitsProcessor(ngram))
             procs.extend(user_procs)
         crit = StoppingCriteriaList(kw.pop("stopping_criteria", None) or [])
         max_time = kw.pop("max_time", None)
         if max_time is not None:
             crit.append(MaxTimeCriteria(max_time=float(max_time)))
         rules = None
-        if len(procs) or len(crit):
-            rules = dict(processors=procs if len(procs) else None, stopping=crit if len(crit) else None)
+        if len(procs) or len(crit) or numbers:
+            rules = dict(processors=procs if len(procs) else None, stopping=crit if len(crit) else None, **numbers)
             if had_eos and not eos_ids:  # the EOS list was emptied above, the model still has an EOS id: hf fills shortened hypotheses with the pad id
                 rules["fill_id"] = int(pad)
         # prompt-lookup decoding [hf generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=n)]: greedy search at batch 1 whose
@@ -586,7 +594,7 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
                 raise ValueError("prompt_lookup_num_tokens and max_matching_ngram_size must be >= 1")
             if input_ids is not None and input_ids.shape[0] > 1:
                 raise ValueError("assisted generate is only supported for batch_size = 1")
-            combo = [n for n, on in (("num_beams > 1", num_beams > 1), ("do_sample=True", do_sample), ("logits processors", len(procs) > 0),
+            combo = [n for n, on in (("num_beams > 1", num_beams > 1), ("do_sample=True", do_sample), ("logits processors", len(procs) > 0 or bool(numbers)),
                                      ("stopping criteria", len(crit) > 0), ("min_new_tokens", min_new > 0)) if on]
             if combo:
                 raise NotImplementedError(f"prompt_lookup_num_tokens with {', '.join(combo)} is not built on the HIP path (greedy search only)")
@@ -613,10 +621,11 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             # hf `_expand_inputs_for_generation`: every prompt is repeated num_return_sequences times (rows of one prompt adjacent)
             emb = emb.repeat_interleave(int(num_return), dim=0)
             attention_mask = attention_mask.repeat_interleave(int(num_return), dim=0)
-        # the captured device step knows ONE eos id and no minimum length; several ids or 0 < min_new_tokens < max_new_tokens run the
-        # same HIP decode step with the stopping rule applied by the host loop (eilev_amd/sampling.py, beam.py)
+        # the plain captured step knows ONE eos id and no minimum length; several ids, 0 < min_new_tokens < max_new_tokens,
+        # repetition_penalty and no_repeat_ngram_size go to the engine with the call: it applies them in the captured step
+        # (include/eilev_rules.h) or, with user processors / stopping criteria, in the host loops (eilev_amd/sampling.py, beam.py)
         eos1 = eos_ids[0] if eos_ids else -1
-        host_rules = len(eos_ids) > 1 or min_new > 0 or rules is not None
+        with_rules = len(eos_ids) > 1 or min_new > 0 or rules is not None
         eng = self.engine()
         if lookup is not None:  # the corpus: the row's visible text ids (no left padding, no video placeholder)
             keep = attention_mask[0] != 0
@@ -630,7 +639,7 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
                                             start_id=int(start))
             return eng.greedy_lookup_decode(emb, attention_mask, text, int(max_new), lookup, lookup_ngram, eos_id=eos_ids, pad_id=int(pad))
         if want_dict:
-            plain_greedy = num_beams == 1 and sampler is None and not host_rules
+            plain_greedy = num_beams == 1 and sampler is None and not with_rules
             if (want_scores or want_logits) and not (plain_greedy and not self._is_t5):
                 raise NotImplementedError("generate(output_scores / output_logits) is served for greedy search on the decoder-only language model only")
             from transformers.generation.utils import GenerateDecoderOnlyOutput
@@ -646,21 +655,21 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             if rules is not None:  # hf's processors see the decoder ids, which begin with the start token
                 rules["prefix"] = torch.full((emb.shape[0], 1), int(start), dtype=torch.int64, device=emb.device)
             if num_beams > 1:
-                return eng.t5_beam(emb, attention_mask, int(max_new), num_beams, float(length_penalty), eos_id=eos_ids if host_rules else eos1,
+                return eng.t5_beam(emb, attention_mask, int(max_new), num_beams, float(length_penalty), eos_id=eos_ids if with_rules else eos1,
                                    pad_id=int(pad), start_id=int(start), early_stopping=early_stopping,
                                    num_return_sequences=int(num_return), sampler=sampler, min_new_tokens=min_new, rules=rules)
-            if sampler is not None or host_rules:
+            if sampler is not None or with_rules:
                 rule = dict(sampler) if sampler is not None else dict(greedy=True)
-                return eng.t5_beam(emb, attention_mask, int(max_new), 1, eos_id=eos_ids if host_rules else eos1, pad_id=int(pad),
+                return eng.t5_beam(emb, attention_mask, int(max_new), 1, eos_id=eos_ids if with_rules else eos1, pad_id=int(pad),
                                    start_id=int(start), sampler=dict(rule, min_new_tokens=min_new), rules=rules)
             return eng.t5_greedy(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad), start_id=int(start))
         if num_beams > 1:
-            return eng.beam_decode(emb, attention_mask, int(max_new), num_beams, float(length_penalty), eos_id=eos_ids if host_rules else eos1,
+            return eng.beam_decode(emb, attention_mask, int(max_new), num_beams, float(length_penalty), eos_id=eos_ids if with_rules else eos1,
                                    pad_id=int(pad), early_stopping=early_stopping, num_return_sequences=int(num_return), sampler=sampler,
                                    min_new_tokens=min_new, rules=rules)
-        if sampler is not None or host_rules:
+        if sampler is not None or with_rules:
             rule = dict(sampler) if sampler is not None else dict(greedy=True)
-            return eng.beam_decode(emb, attention_mask, int(max_new), 1, eos_id=eos_ids if host_rules else eos1, pad_id=int(pad),
+            return eng.beam_decode(emb, attention_mask, int(max_new), 1, eos_id=eos_ids if with_rules else eos1, pad_id=int(pad),
                                    sampler=dict(rule, min_new_tokens=min_new), rules=rules)
         return eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad))
 
