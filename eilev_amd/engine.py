@@ -43,6 +43,10 @@ class HipEngine:
         self.sample_stats = None     # per sampling call: dict(path="device" | "host", steps=generated tokens per row)
         self.device_rules = True     # greedy / beam search with repetition_penalty, no_repeat_ngram_size, min_new_tokens or several EOS ids: the
         self.rules_stats = None      # rules run in the captured step (include/eilev_rules.h); per such call: dict(path="device" | "host", steps=)
+        self.beam_device_loop = True     # plain beam search selects on the device (beam.py beam_search_device); False: the host loop beam_search
+        self.beam_topk_kernel = True     # its per-row top-k is eilev_topk_logprob; False: torch ops
+        self.beam_advance_kernel = True  # its bookkeeping of a step is eilev_beam_advance; False: torch ops
+        self.beam_capture = False        # replay the fused step (both kernels) from a hipGraph; it buys nothing per token there
         self.parts = tuple(parts)
         if lm_weights not in ("bf16", "fp8", "fp8_mfma"):
             raise ValueError("lm_weights must be 'bf16', 'fp8' (e4m3 weights, bf16 activations) or 'fp8_mfma' (e4m3 weights AND per-token "
@@ -619,109 +623,24 @@ class HipEngine:
 
     def greedy_decode(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, use_graph=True,
                       poll_every=8, return_step_logits=False):
-        """Prefill + KV-cached greedy decode [ref:eilev/model/v2.py:318-322 -> hf generation/utils.py:2783-2941].
+        """Prefill + KV-cached greedy decode [ref:eilev/model/v2.py:318-322 -> hf generation/utils.py:2783-2941]: _select_decode_device
+        with the decode step's own arg-max as the selection.
 
         Returns int64 (B, n_steps) of NEW tokens only (OPT path)."""
-        d = self.dims
-        B, L, _ = inputs_embeds.shape
+        from .sampling import eos_list
+
+        B = inputs_embeds.shape[0]
         if max_new_tokens <= 0:
             return torch.empty((B, 0), dtype=torch.int64, device=self.device)
         if B > 32:
-            # the decode kernels stream the weights once for up to 32 rows: larger batches run as consecutive 32-row decodes (the
-            # reference accepts any batch size); rows that stop early are padded like HF pads them
             if return_step_logits:
                 raise NotImplementedError("return_step_logits with more than 32 rows")
-            parts = [self.greedy_decode(inputs_embeds[i:i + 32], attention_mask[i:i + 32], max_new_tokens, eos_id, pad_id, use_graph, poll_every)
-                     for i in range(0, B, 32)]
-            n = max(p.shape[1] for p in parts)
-            return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
-        cap = L + max_new_tokens
-        n_dec = max_new_tokens - 1
-        if n_dec > 0:
-            self.ensure_stream_layout(B)
-        graphable = use_graph and n_dec > 1 and not return_step_logits
-        # The captured decode step only depends on buffer ADDRESSES and on (B, L, cap, eos, pad): keep the most recent
-        # graph with its buffers (KV cache, state words, token / output buffers) and reuse it for calls of the same shape
-        key = (B, L, cap, max_new_tokens, int(eos_id), int(pad_id))
-        ent = self._dec_cache if (graphable and self._dec_cache is not None and self._dec_cache["key"] == key) else None
-        if ent is None:
-            ent = dict(key=key, graph=None,
-                       am=torch.empty((B, L), dtype=torch.int32, device=self.device),
-                       n_valid=torch.empty(B, dtype=torch.int32, device=self.device),
-                       kv=self.new_kv_cache(B, cap),
-                       state=torch.zeros(2, dtype=torch.int32, device=self.device),
-                       finished=torch.zeros(B, dtype=torch.uint8, device=self.device),
-                       tokens=torch.zeros(B, dtype=torch.int64, device=self.device),
-                       out=torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device),
-                       logits=torch.empty((B, d.vocab), dtype=torch.float32, device=self.device),
-                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1)))
-            if graphable:
-                self._dec_cache = None  # drop the previous entry (its KV cache) before keeping this one
-                self._dec_cache = ent
-        am, n_valid, kv = ent["am"], ent["n_valid"], ent["kv"]
-        state, finished, tokens, out, logits, ws = ent["state"], ent["finished"], ent["tokens"], ent["out"], ent["logits"], ent["ws"]
-        am.copy_(attention_mask.to(self.device, torch.int32))
-        n_valid.copy_(am.sum(dim=1))
-        state.zero_()
-        finished.zero_()
-        out.fill_(int(pad_id))
-        last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
-        if self.timing is not None:  # optional phase stamps for bench.py (events on the launch stream, no sync)
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.timing.append(("prefill_done", ev))
-        step_logits = [last.clone()] if return_step_logits else None
-        abi.check(self.lib.eilev_greedy_select(_ptr(last), B, d.vocab, _ptr(state), _ptr(finished), eos_id, pad_id,
-                                               _ptr(tokens), _ptr(out), max_new_tokens, self._stream()), "eilev_greedy_select")
-
-        def one_step():
-            abi.check(self.lib.eilev_opt_decode_step(
-                C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), B, L, _ptr(kv), cap,
-                _ptr(logits), _ptr(finished), eos_id, pad_id, _ptr(out), max_new_tokens, _ptr(ws), ws.numel(),
-                self._stream()), "eilev_opt_decode_step")
-
-        graph = ent["graph"] if graphable else None
-        if graphable and graph is None:
-            # every per-step quantity is read from `state` on the device, so ONE captured step replays for all
-            graph = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream(self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                if not self._decode_warm:  # once per engine: a step outside capture (lazy module loading of the kernels)
-                    snap = (state.clone(), finished.clone(), tokens.clone(), out.clone())
-                    one_step()
-                    state.copy_(snap[0]); finished.copy_(snap[1]); tokens.copy_(snap[2]); out.copy_(snap[3])
-                    self._decode_warm = True
-                    # it wrote KV slot L (state said step 1): the captured replay rewrites the same slot
-                with torch.cuda.graph(graph, stream=side):
-                    one_step()
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            ent["graph"] = graph
-            # capture does not execute: nothing ran yet for step 1
-        done_steps = 0
-        while done_steps < n_dec:
-            if graph is not None:
-                graph.replay()
-            else:
-                one_step()
-                if return_step_logits:
-                    step_logits.append(logits.clone())
-            done_steps += 1
-            if eos_id >= 0 and (done_steps % poll_every == 0) and int(state[1].item()) == 0:
-                break
-        ids = out
-        if eos_id >= 0:
-            # HF stops as soon as every row has emitted EOS: trim to that length
-            is_eos = ids == eos_id
-            first = torch.where(is_eos.any(dim=1), is_eos.float().argmax(dim=1) + 1,
-                                torch.full((B,), max_new_tokens, device=self.device))
-            n = int(first.max().item())
-            ids = ids[:, :n]
-        else:
-            ids = ids[:, : 1 + done_steps]
-        ids = ids.clone()  # `out` belongs to the cached graph entry
-        return (ids, step_logits) if return_step_logits else ids
-
+            return self._chunked_rows(lambda i, j: self.greedy_decode(inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, use_graph,
+                                                                      poll_every), B, pad_id)
+        trace = [] if return_step_logits else None
+        ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_list(eos_id), pad_id, ("greedy",), None, None, use_graph,
+                                         poll_every, trace)
+        return (ids, trace) if return_step_logits else ids
 
     def _pld_buffers(self, text_ids, max_new_tokens, k, vocab):
         """Device state of one prompt-lookup generation (include/eilev_pld.h): corpus (text ids, room for max_new ids), its length, the
@@ -822,6 +741,14 @@ class HipEngine:
             raise NotImplementedError("num_beams > 32")
         from .sampling import eos_list
 
+        # The fused form of the device loop, stated once as the two facts used below: the per-row top-k kernel takes this call (its vocabulary,
+        # `keep` candidates per row), and so does the kernel that advances the hypotheses
+        eos_l = eos_list(eos_id)
+        keep = max(2, 1 + len(eos_l)) * num_beams
+        gen_cap = max(1, max_new_tokens)
+        topk_ok = self.beam_topk_kernel and d.vocab <= 65536 and d.vocab % 4 == 0 and keep <= 64
+        advance_ok = topk_ok and self.beam_advance_kernel and num_beams * keep <= 2048 and gen_cap * num_beams <= 2048 and len(eos_l) <= 8
+        device_loop = sampler is None and num_beams > 1 and self.beam_device_loop
         rules_kw, with_rules, rules_in = None, False, rules
         if sampler is not None and num_beams == 1 and not sampler.get("greedy"):
             sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id, trace)
@@ -829,36 +756,29 @@ class HipEngine:
                 return self.sample_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, **dev_kw)
         else:
             # greedy search (num_beams == 1, sampler = dict(greedy=True)) and beam search: the rules run on the device when the route says so and,
-            # for beams, when the search takes the fused topk_fn + advance_fn form below; beam-search sampling keeps the host loop
-            keep = max(2, 1 + len(eos_list(eos_id))) * num_beams
-            fused_ok = (sampler is None and num_beams > 1 and getattr(self, "beam_device_loop", True) and getattr(self, "beam_topk_kernel", True) and
-                        getattr(self, "beam_advance_kernel", True) and keep <= abi.RULES_MAX_KEEP and num_beams * keep <= 2048 and
-                        max(1, max_new_tokens) * num_beams <= 2048)
+            # for beams, when the search takes the fused form; beam-search sampling keeps the host loop
             min_new = int(min_new_tokens) if sampler is None else int(sampler.get("min_new_tokens", 0) or 0)
-            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, trace, allow_device=fused_ok or (sampler is not None and num_beams == 1))
+            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, trace,
+                                                            allow_device=(device_loop and advance_ok) or (sampler is not None and num_beams == 1))
             if rules_kw is not None and num_beams == 1:
                 return self.rules_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, **rules_kw)
         if R > 32:
-            # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are
-            # independent in beam search); shorter results are padded with pad_id like HF pads finished hypotheses
-            per = max(1, 32 // num_beams)
+            # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are independent in beam search)
             if trace is not None:
                 raise ValueError("trace: at most 32 decode rows")
             if rules and rules.get("prefix") is not None:
                 raise NotImplementedError("prefix ids with more than 32 decode rows")
             if rules_kw is not None or with_rules:  # (every part is routed again: it gets the caller's rules, numbers included)
                 rules = rules_in
-            parts = [self.beam_decode(inputs_embeds[i:i + per], attention_mask[i:i + per], max_new_tokens, num_beams, length_penalty, eos_id,
-                                      pad_id, early_stopping, num_return_sequences, sampler, min_new_tokens, use_graph, None, rules) for i in range(0, B, per)]
-            n = max(p.shape[1] for p in parts)
-            return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
+            return self._chunked_rows(lambda i, j: self.beam_decode(
+                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, num_beams, length_penalty, eos_id, pad_id, early_stopping, num_return_sequences,
+                sampler, min_new_tokens, use_graph, None, rules), B, pad_id, per=max(1, 32 // num_beams))
         am = attention_mask.to(self.device, torch.int32).contiguous()
         # The KV cache is never moved (round 3; before: a torch index_select of the whole cache per step, 1.6 GB at 5 beams x L = 960):
         # the prompt's keys / values stay in the prefill cache (one row per SAMPLE, capacity L), generated tokens go to a generation
         # cache (one row per beam slot, capacity max_new_tokens) and `anc[g][r]` names the slot holding token g of the hypothesis now in
         # row r — include/eilev.h eilev_opt_decode_step_beam.  A step = gather of that small table by the parents + one captured launch.
         last, _, kv_prompt = self.prefill(inputs_embeds, am, kv_capacity=L)
-        gen_cap = max(1, max_new_tokens)
         kv_gen = torch.empty(int(self.lib.eilev_opt_kv_cache_bytes(C.byref(d), R, gen_cap)), dtype=torch.uint8, device=self.device)
         anc = torch.zeros((gen_cap, R), dtype=torch.int32, device=self.device)
         ident32 = torch.arange(R, dtype=torch.int32, device=self.device)
@@ -886,20 +806,9 @@ class HipEngine:
             if t == 0:
                 state[0] = 1  # (the call increments it: every per-step quantity is on the device, so ONE captured step replays)
             if use_graph and max_new_tokens > 2:
-                if graph[0] is None:
-                    if not self._decode_warm:
-                        keep = state.clone()
-                        launch()  # once per engine outside capture (lazy module loading); it rewrote this step's slot only
-                        state.copy_(keep)
-                        self._decode_warm = True
-                    gph = torch.cuda.CUDAGraph()
-                    side = torch.cuda.Stream(self.device)
-                    side.wait_stream(torch.cuda.current_stream(self.device))
-                    with torch.cuda.stream(side):
-                        with torch.cuda.graph(gph, stream=side):
-                            launch()
-                    torch.cuda.current_stream(self.device).wait_stream(side)
-                    graph[0] = gph
+                if graph[0] is None:  # (once per engine the launch also runs outside capture; it rewrote this step's slot only)
+                    graph[0] = self._capture_step(launch, (state,), warm=not self._decode_warm)
+                    self._decode_warm = True
                 graph[0].replay()
             else:
                 launch()
@@ -907,8 +816,7 @@ class HipEngine:
                 trace.append((next_tokens.clone(), beam_src.clone(), logits.clone()))
             return logits
 
-        if sampler is None and (rules_kw is not None or (not rules and int(min_new_tokens) == 0)) and trace is None and num_beams > 1 and \
-                getattr(self, "beam_device_loop", True):
+        if device_loop and (rules_kw is not None or (not rules and int(min_new_tokens) == 0)) and trace is None:
             # (r4) plain beam search — the sample script's call: selection, ancestor-table update and the decode step as ONE captured graph per
             # generated token, nothing indexed by the step on the host (eilev_amd/beam.py::beam_search_device)
             from .beam import beam_search_device
@@ -924,9 +832,8 @@ class HipEngine:
                 launch()
                 tpos.add_(1)
 
-            keep = max(2, 1 + len(eos_list(eos_id))) * num_beams
             topk_fn = None
-            if d.vocab <= 65536 and d.vocab % 4 == 0 and keep <= 64 and getattr(self, "beam_topk_kernel", True):
+            if topk_ok:
                 row_lp = torch.empty((R, keep), dtype=torch.float32, device=self.device)
                 row_tok = torch.empty((R, keep), dtype=torch.int32, device=self.device)
 
@@ -936,9 +843,7 @@ class HipEngine:
                     return row_lp, row_tok
 
             advance_fn = None
-            if topk_fn is not None and num_beams * keep <= 2048 and gen_cap * num_beams <= 2048 and len(eos_list(eos_id)) <= 8 and \
-                    getattr(self, "beam_advance_kernel", True):
-                eos_l = eos_list(eos_id)
+            if advance_ok:
                 eos_arr = (C.c_int64 * max(1, len(eos_l)))(*eos_l)
                 scratch = torch.empty(int(self.lib.eilev_beam_scratch_bytes(B, num_beams, keep, max_new_tokens)), dtype=torch.uint8, device=self.device)
 
@@ -955,14 +860,13 @@ class HipEngine:
             # with the two selection kernels a step is ONE C call that enqueues ~260 kernels (2.5 ms of GPU work): capturing it buys nothing per
             # token (2.565 vs 2.554 ms) and costs ~1.2 ms per generate() call — replayed graphs only on request (`engine.beam_capture = True`)
             # or when the selection runs as torch ops
-            capture = use_graph and (advance_fn is None or getattr(self, "beam_capture", False))
+            capture = use_graph and (advance_fn is None or self.beam_capture)
             if rules_kw is not None:
                 # the rules of the call inside the per-row selection (eilev_rules_topk_logprob): row r's history is run_seq[r, 0 .. cur), which
-                # eilev_beam_advance keeps in place, and cur = state[0] - 1 is the decode step's device counter
-                assert advance_fn is not None, "the route checked the conditions of the fused form"
+                # eilev_beam_advance keeps in place, and cur = state[0] - 1 is the decode step's device counter (allow_device: advance_ok holds)
                 rl = abi.load_rules()
                 p_rules = abi.rules_params(rules_kw["repetition_penalty"], rules_kw["no_repeat_ngram_size"], rules_kw["min_new_tokens"], max_new_tokens,
-                                           eos_list(eos_id), pad_id, -1, 0, 0)
+                                           eos_l, pad_id, -1, 0, 0)
 
                 def topk_fn(buf, run_score, run_seq, cur_t):  # noqa: F811
                     abi.check(rl.eilev_rules_topk_logprob(C.byref(p_rules), _ptr(buf), _ptr(run_score), R, d.vocab, keep, _ptr(state), _ptr(run_seq),
@@ -979,17 +883,20 @@ class HipEngine:
             from .sampling import sample_loop
 
             ids = sample_loop(step, last, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
-            self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
-            if with_rules:
-                self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
-            return ids
-        ids = beam_search(step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
-                          num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
-        if sampler is not None:  # beam-search sampling
-            self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
-        elif with_rules:
-            self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
+        else:
+            ids = beam_search(step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
+                              num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
+        self._host_stats(ids, sampler, num_beams, with_rules)
         return ids
+
+    def _host_stats(self, ids, sampler, num_beams, with_rules):
+        """What a call that ran one of the host loops (sample_loop, beam_search) records: sample_stats when it drew, rules_stats when it
+        carried rules (beam-search sampling records the former only)."""
+        rec = dict(path="host", steps=int(ids.shape[1]))
+        if sampler is not None:
+            self.sample_stats = rec
+        if with_rules and (sampler is None or num_beams == 1):
+            self.rules_stats = dict(rec)
 
     def sample_decode(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
                       generator=None, repetition_penalty=1.0, min_new_tokens=0):
@@ -1007,21 +914,33 @@ class HipEngine:
         from .sampling import eos_list
 
         sampler = dict(sampler)
-        pen = float(sampler.pop("repetition_penalty", None) or 1.0)
-        ngram = int(sampler.pop("no_repeat_ngram_size", None) or 0)
-        host_only = bool(rules) and (rules.get("processors") is not None or rules.get("stopping") is not None)
-        if (getattr(self, "device_sampling", True) and not host_only and trace is None and not sampler.get("greedy") and
+        pen, ngram, host_only, to_host = HipEngine._rule_numbers(sampler, rules)
+        if (self.device_sampling and not host_only and trace is None and not sampler.get("greedy") and
                 len(eos_list(eos_id)) <= abi.SAMPLE_MAX_EOS and abi.sample_supported(vocab) and (not ngram or abi.rules_supported(vocab))):
             dev_kw = dict(temperature=sampler.get("temperature", 1.0), top_k=sampler.get("top_k", 50), top_p=sampler.get("top_p", 1.0),
                           repetition_penalty=pen, min_new_tokens=sampler.get("min_new_tokens", 0), generator=sampler.get("generator"))
             if ngram:
                 dev_kw["no_repeat_ngram_size"] = ngram
             return sampler, rules, dev_kw
-        if pen != 1.0 or ngram:
-            rules = dict(rules or {})
-            rules["processors"] = self._host_processors(pen, ngram, rules.get("processors"))
-            rules.setdefault("stopping", None)
-        return sampler, rules, None
+        return sampler, to_host(rules), None
+
+    @staticmethod
+    def _rule_numbers(carrier, rules):
+        """Head and tail of the two routes.  Pops the numbers repetition_penalty / no_repeat_ngram_size from ``carrier`` (the route's own copy
+        of the dict that carries them).  Returns (pen, ngram, host_only, to_host): host_only — ``rules`` holds a user processor or a stopping
+        criterion; to_host(rules) — the rules with the numbers as transformers' processors again, the form the host loops take."""
+        pen = float(carrier.pop("repetition_penalty", None) or 1.0)
+        ngram = int(carrier.pop("no_repeat_ngram_size", None) or 0)
+        host_only = bool(rules) and (rules.get("processors") is not None or rules.get("stopping") is not None)
+
+        def to_host(rules):
+            if pen != 1.0 or ngram:
+                rules = dict(rules or {})
+                rules["processors"] = HipEngine._host_processors(pen, ngram, rules.get("processors"))
+                rules.setdefault("stopping", None)
+            return rules
+
+        return pen, ngram, host_only, to_host
 
     @staticmethod
     def _host_processors(pen, ngram, more=None):
@@ -1046,18 +965,13 @@ class HipEngine:
         from .sampling import eos_list
 
         rules = dict(rules or {})
-        pen = float(rules.pop("repetition_penalty", None) or 1.0)
-        ngram = int(rules.pop("no_repeat_ngram_size", None) or 0)
-        host_only = rules.get("processors") is not None or rules.get("stopping") is not None
+        pen, ngram, host_only, to_host = HipEngine._rule_numbers(rules, rules)
         n_eos = len(eos_list(eos_id))
         with_rules = pen != 1.0 or ngram > 0 or int(min_new_tokens) > 0 or n_eos > 1 or host_only
-        if (with_rules and allow_device and getattr(self, "device_rules", True) and not host_only and trace is None and
+        if (with_rules and allow_device and self.device_rules and not host_only and trace is None and
                 n_eos <= abi.RULES_MAX_EOS and abi.rules_supported(vocab)):
             return dict(repetition_penalty=pen, no_repeat_ngram_size=ngram, min_new_tokens=int(min_new_tokens)), (rules or None), True
-        if pen != 1.0 or ngram:
-            rules["processors"] = self._host_processors(pen, ngram, rules.get("processors"))
-            rules.setdefault("stopping", None)
-        return None, (rules or None), with_rules
+        return None, (to_host(rules) or None), with_rules
 
     def _sample_setup(self, R, vocab, max_new_tokens, generator, uniforms, **spec):
         """The sampling library, the uniforms of a whole call — (max_new, R), drawn ONCE on the generator's device — and a function that makes
@@ -1099,18 +1013,32 @@ class HipEngine:
     def _rules_ban(self, rl, params, logits, R, vocab, state, out):
         abi.check(rl.eilev_rules_ban(C.byref(params), _ptr(logits), R, vocab, _ptr(state), _ptr(out), self._stream()), "eilev_rules_ban")
 
-    def _trim_sampled(self, out, n, eos, pad_id):
-        """The first n columns of `out`, cut where every row has drawn an EOS id (hf stops there); finished rows already hold the pad id."""
+    def _stamp(self, name):
+        """Optional phase stamps for bench.py (events on the launch stream, no sync)."""
+        if self.timing is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.timing.append((name, ev))
+
+    def _greedy_select(self, logits, R, vocab, state, finished, eos_id, pad_id, tokens, out):
+        abi.check(self.lib.eilev_greedy_select(_ptr(logits), R, vocab, _ptr(state), _ptr(finished), eos_id, pad_id, _ptr(tokens), _ptr(out), out.shape[1],
+                                               self._stream()), "eilev_greedy_select")
+
+    @staticmethod
+    def _trim_at_eos(out, n, eos):
+        """The first n columns of `out` (n = the steps done), cut after the column where the last row emits its first EOS id (hf stops there);
+        finished rows already hold the pad id.  A copy: `out` may belong to a cached graph entry."""
         ids = out[:, :n]
         if eos:
-            is_eos = torch.isin(ids, torch.tensor(eos, dtype=torch.int64, device=self.device))
-            first = torch.where(is_eos.any(dim=1), is_eos.float().argmax(dim=1) + 1, torch.full((ids.shape[0],), n, device=self.device))
+            is_eos = torch.isin(ids, torch.tensor(eos, dtype=torch.int64, device=out.device))
+            first = torch.where(is_eos.any(dim=1), is_eos.float().argmax(dim=1) + 1, torch.full((ids.shape[0],), n, device=out.device))
             ids = ids[:, : int(first.max().item())]
         return ids.clone()
 
-    def _capture_sample_step(self, one_step, buffers, warm):
-        """One decode-and-draw step as a hipGraph.  ``warm``: run the step once outside capture first (lazy module loading) and put
-        ``buffers`` (the words the step advances) back."""
+    def _capture_step(self, one_step, buffers, warm):
+        """One decode step as a hipGraph, captured on a side stream that rejoins the current one.  ``warm``: run the step once outside capture
+        first (lazy module loading of the kernels) and put ``buffers`` (the words the step advances) back; the cache slot it wrote is the
+        one the first replay rewrites.  Capture does not execute: nothing has run for the step afterwards."""
         graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
@@ -1125,7 +1053,7 @@ class HipEngine:
         torch.cuda.current_stream(self.device).wait_stream(side)
         return graph
 
-    def _run_sample_steps(self, n_steps, one_step, graph, state, eos, poll_every, trace, logits, poll_last=False):
+    def _run_steps(self, n_steps, one_step, graph, state, eos, poll_every, trace, logits, poll_last=False):
         """Replay (or launch) up to n_steps steps; with EOS ids, read state[1] back every poll_every steps and stop once no row is left.
         Returns the steps done."""
         done = 0
@@ -1141,27 +1069,34 @@ class HipEngine:
                 break
         return done
 
-    def _chunked_rows(self, call, B, stats_name, pad_id):
-        """More than 32 rows: ``call(i, j)`` on consecutive 32-row slices (as greedy_decode), shorter parts padded like hf pads rows that
-        stopped early; the stats record of the whole call holds the longest part's steps."""
+    def _chunked_rows(self, call, B, pad_id, stats_name=None, per=32):
+        """More decode rows than one call takes (the decode kernels stream the weights once for up to 32 rows; the reference accepts any batch
+        size): ``call(i, j)`` on consecutive slices of ``per`` samples, shorter parts padded like hf pads rows that stopped early.
+        ``stats_name``: the stats record of the whole call holds the longest part's steps."""
         parts, n_steps = [], 0
-        for i in range(0, B, 32):
-            parts.append(call(i, min(i + 32, B)))
-            n_steps = max(n_steps, getattr(self, stats_name)["steps"])
+        for i in range(0, B, per):
+            parts.append(call(i, min(i + per, B)))
+            if stats_name:
+                n_steps = max(n_steps, getattr(self, stats_name)["steps"])
         n = max(p.shape[1] for p in parts)
-        setattr(self, stats_name, dict(path="device", steps=n_steps))
+        if stats_name:
+            setattr(self, stats_name, dict(path="device", steps=n_steps))
         return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
 
     def _select_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace):
-        """greedy_decode's structure — one KV cache of capacity L + max_new, the stream layout, ONE captured step replayed per token — with a
-        selection of the caller's after the decode step (the draw of sample_decode_device, the rules + arg-max of rules_decode_device).  The
-        decode step's own arg-max writes to scratch buffers (eos -1); the selection then overwrites `tokens`.
+        """The cached OPT decode: one KV cache of capacity L + max_new, the stream layout, ONE captured step replayed per token (every per-step
+        quantity is read from `state` on the device).  ``bind is None`` (greedy_decode): the decode step's own arg-max selects, the first token
+        comes from eilev_greedy_select on the prefill's logits.  Else a selection of the caller's runs after the decode step (the draw of
+        sample_decode_device, the rules + arg-max of rules_decode_device): the step's arg-max writes to scratch buffers (eos -1) and the
+        selection then overwrites `tokens`.
 
-        ``key``: what the captured step depends on beside the shape (the parameter block is passed by value): one cached entry, in
-        greedy_decode's slot (a call of the other kind replaces it, so one KV cache is kept at a time).  ``extra(B)``: the selection's own
+        The captured step only depends on buffer ADDRESSES and on ``key`` — the kind of the call and what its selection depends on (the
+        parameter block is passed by value) — plus (B, L, cap, eos, pad): the most recent graph is kept with its buffers in ONE slot and reused
+        by calls of the same key (a call of another kind replaces it, so one KV cache is kept at a time).  ``extra(B)``: the selection's own
         buffers of a new entry.  ``bind(ent) -> (first(logits), step(logits))``: called once per call with the entry's buffers; `first` selects
         from the prefill's logits (state[0] = 0, it finalizes the step itself), `step` from the decode step's (which has already advanced
-        state[0]).  At most 32 rows.  Returns int64 (B, n) new tokens."""
+        state[0]).  ``trace``: a list that receives the prefill's logits and a copy of every eager step's; it turns capture off.  At most 32
+        rows.  Returns int64 (B, n) new tokens."""
         d = self.dims
         B, L, _ = inputs_embeds.shape
         cap = L + max_new_tokens
@@ -1180,10 +1115,11 @@ class HipEngine:
                        finished=torch.zeros(B, dtype=torch.uint8, device=self.device),
                        tokens=torch.zeros(B, dtype=torch.int64, device=self.device),
                        out=torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device),
-                       argmax_out=torch.zeros((B, max_new_tokens), dtype=torch.int64, device=self.device),   # the decode step's own selection:
-                       argmax_fin=torch.zeros(B, dtype=torch.uint8, device=self.device),                     # never read
                        logits=torch.empty((B, d.vocab), dtype=torch.float32, device=self.device),
-                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1)), **extra(B))
+                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1)))
+            if bind is not None:  # the decode step's own selection goes to buffers that are never read
+                ent.update(argmax_out=torch.zeros((B, max_new_tokens), dtype=torch.int64, device=self.device),
+                           argmax_fin=torch.zeros(B, dtype=torch.uint8, device=self.device), **extra(B))
             if graphable:
                 self._dec_cache = None  # drop the previous entry (its KV cache) before keeping this one
                 self._dec_cache = ent
@@ -1194,12 +1130,14 @@ class HipEngine:
         state.zero_()
         finished.zero_()
         out.fill_(int(pad_id))
-        first, step = bind(ent)
+        if bind is None:
+            step_fin, step_eos, step_out = finished, (eos[0] if eos else -1), out
+            first, step = (lambda lg: self._greedy_select(lg, B, d.vocab, state, finished, step_eos, pad_id, tokens, out)), (lambda lg: None)
+        else:
+            step_fin, step_eos, step_out = ent["argmax_fin"], -1, ent["argmax_out"]
+            first, step = bind(ent)
         last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
-        if self.timing is not None:  # optional phase stamps for bench.py (events on the launch stream, no sync)
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.timing.append(("prefill_done", ev))
+        self._stamp("prefill_done")
         if trace is not None:
             trace.append(last.clone())
         first(last)
@@ -1207,16 +1145,16 @@ class HipEngine:
         def one_step():
             abi.check(self.lib.eilev_opt_decode_step(
                 C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), B, L, _ptr(kv), cap,
-                _ptr(logits), _ptr(ent["argmax_fin"]), -1, pad_id, _ptr(ent["argmax_out"]), max_new_tokens, _ptr(ws), ws.numel(),
+                _ptr(logits), _ptr(step_fin), step_eos, pad_id, _ptr(step_out), max_new_tokens, _ptr(ws), ws.numel(),
                 self._stream()), "eilev_opt_decode_step")
             step(logits)
 
         graph = ent["graph"] if graphable else None
-        if graphable and graph is None:  # (once per engine the step also runs outside capture: lazy module loading of the kernels)
-            graph = ent["graph"] = self._capture_sample_step(one_step, (state, finished, tokens, out), warm=not self._decode_warm)
+        if graphable and graph is None:  # (once per engine the step also runs outside capture; it wrote KV slot L, as the first replay does)
+            graph = ent["graph"] = self._capture_step(one_step, (state, finished, tokens, out), warm=not self._decode_warm)
             self._decode_warm = True
-        done_steps = self._run_sample_steps(n_dec, one_step, graph, state, eos, poll_every, trace, logits)
-        return self._trim_sampled(out, 1 + done_steps, eos, pad_id)
+        done_steps = self._run_steps(n_dec, one_step, graph, state, eos, poll_every, trace, logits)
+        return self._trim_at_eos(out, 1 + done_steps, eos)
 
     def sample_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
                              repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None,
@@ -1241,7 +1179,7 @@ class HipEngine:
                 raise ValueError("trace: at most 32 decode rows")
             return self._chunked_rows(lambda i, j: self.sample_decode_device(
                 inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, temperature, top_k, top_p, repetition_penalty, min_new_tokens,
-                None, use_graph, poll_every, None, uni_all[:, i:j], ngram), B, "sample_stats", pad_id)
+                None, use_graph, poll_every, None, uni_all[:, i:j], ngram), B, pad_id, "sample_stats")
         rl, ban_params = self._rules_setup(d.vocab, max_new_tokens, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id) if ngram else (None, None)
 
         def extra(rows):
@@ -1287,7 +1225,7 @@ class HipEngine:
                 raise ValueError("trace: at most 32 decode rows")
             return self._chunked_rows(lambda i, j: self.rules_decode_device(
                 inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, repetition_penalty, ngram, min_new_tokens, use_graph, poll_every),
-                B, "rules_stats", pad_id)
+                B, pad_id, "rules_stats")
 
         def bind(ent):
             def select(p):
@@ -1301,12 +1239,15 @@ class HipEngine:
         return ids
 
     def _t5_select_device(self, inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id, bind, use_graph, poll_every, trace):
-        """t5_greedy's structure with a selection of the caller's in place of eilev_greedy_select: ``bind(state, finished, tokens, out) ->
-        step(logits)``.  At most 32 rows.  Returns the new ids (B, n), without the start token."""
+        """The flan-t5 decode loop: encoder and cross K/V once, then one decoder step + the caller's selection (position and bookkeeping read
+        from a device `state` word) captured into a hipGraph and replayed.  ``bind(state, finished, tokens, out) -> step(logits)``.  At most
+        32 rows.  Returns the new ids (B, n), without the start token."""
         d = self.t5dims
         B = inputs_embeds.shape[0]
         enc = self.t5_encode(inputs_embeds, attention_mask)
+        self._stamp("t5_encoder_done")
         ckv = self.t5_cross_kv(enc)
+        self._stamp("prefill_done")  # encoder + cross K/V = what the prefill is for the decoder-only model
         L = enc.shape[1]
         cap = max_new_tokens
         am = attention_mask.to(self.device, torch.int32).contiguous()
@@ -1326,9 +1267,9 @@ class HipEngine:
 
         graph = None
         if use_graph and max_new_tokens > 1 and trace is None:  # (the warm-up step only touches cache slot 0, which the replay rewrites)
-            graph = self._capture_sample_step(one_step, (state, finished, tokens, out), warm=True)
-        n = self._run_sample_steps(max_new_tokens, one_step, graph, state, eos, poll_every, trace, logits, poll_last=True)
-        return self._trim_sampled(out, n, eos, pad_id)
+            graph = self._capture_step(one_step, (state, finished, tokens, out), warm=True)
+        n = self._run_steps(max_new_tokens, one_step, graph, state, eos, poll_every, trace, logits, poll_last=True)
+        return self._trim_at_eos(out, n, eos)
 
     def t5_sample_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, temperature=1.0, top_k=50, top_p=1.0,
                          repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None,
@@ -1353,7 +1294,7 @@ class HipEngine:
                 raise ValueError("trace: at most 32 decode rows")
             ids = self._chunked_rows(lambda i, j: self.t5_sample_device(
                 inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, start_id, temperature, top_k, top_p, repetition_penalty,
-                min_new_tokens, None, use_graph, poll_every, None, uni[:, i:j], ngram)[:, 1:], B, "sample_stats", pad_id)
+                min_new_tokens, None, use_graph, poll_every, None, uni[:, i:j], ngram)[:, 1:], B, pad_id, "sample_stats")
             return torch.cat((start, ids), dim=1)
         rl, ban_params = self._rules_setup(d.vocab, max_new_tokens, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id,
                                            prefix_id=int(start_id)) if ngram else (None, None)
@@ -1391,7 +1332,7 @@ class HipEngine:
                 raise ValueError("trace: at most 32 decode rows")
             ids = self._chunked_rows(lambda i, j: self.t5_rules_device(
                 inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, start_id, repetition_penalty, ngram, min_new_tokens, use_graph,
-                poll_every)[:, 1:], B, "rules_stats", pad_id)
+                poll_every)[:, 1:], B, pad_id, "rules_stats")
             return torch.cat((start, ids), dim=1)
         p_step = params(0, 1)
         ids = self._t5_select_device(
@@ -1485,67 +1426,18 @@ class HipEngine:
 
     def t5_greedy(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, use_graph=True, poll_every=8):
         """Greedy generation for the encoder-decoder LM [ref:eilev/model/v2.py:318-322 -> hf _sample]: returns decoder ids
-        (B, 1 + n) INCLUDING the start token, like HF does for encoder-decoder models.  One decoder step + token selection
-        (position and bookkeeping read from a device `state` word) is captured into a hipGraph and replayed."""
-        d = self.t5dims
+        (B, 1 + n) INCLUDING the start token, like HF does for encoder-decoder models.  _t5_select_device with eilev_greedy_select as
+        the selection."""
+        from .sampling import eos_list
 
-        def stamp(name):  # optional phase stamps for bench.py (events on the launch stream, no sync)
-            if self.timing is not None:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                self.timing.append((name, ev))
-
-        enc = self.t5_encode(inputs_embeds, attention_mask)
-        stamp("t5_encoder_done")
-        ckv = self.t5_cross_kv(enc)
-        stamp("prefill_done")  # encoder + cross K/V = what the prefill is for the decoder-only model
-        B, L, _ = enc.shape
-        if max_new_tokens <= 0:
-            return torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
-        cap = max_new_tokens
-        am = attention_mask.to(self.device, torch.int32).contiguous()
-        skv = torch.empty(int(self.lib.eilev_t5_self_kv_bytes(C.byref(d), B, cap)), dtype=torch.uint8, device=self.device)
-        state = torch.zeros(2, dtype=torch.int32, device=self.device)
-        finished = torch.zeros(B, dtype=torch.uint8, device=self.device)
-        tokens = torch.full((B,), int(start_id), dtype=torch.int64, device=self.device)
-        out = torch.full((B, max_new_tokens), int(pad_id), dtype=torch.int64, device=self.device)
-        logits = torch.empty((B, d.vocab), dtype=torch.float32, device=self.device)
-        nb = self.lib.eilev_t5_workspace_bytes(C.byref(d), B, 1, max(L, cap))
-        ws = self._workspace("t5dec", nb)
-
-        def one_step():
-            abi.check(self.lib.eilev_t5_decode_step(C.byref(d), C.byref(self.pack.t5), _ptr(tokens), _ptr(state), _ptr(am), B, _ptr(skv), cap,
-                                                    _ptr(ckv), L, _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_t5_decode_step")
-            abi.check(self.lib.eilev_greedy_select(_ptr(logits), B, d.vocab, _ptr(state), _ptr(finished), eos_id, pad_id, _ptr(tokens),
-                                                   _ptr(out), max_new_tokens, self._stream()), "eilev_greedy_select")
-
-        graph = None
-        if use_graph and max_new_tokens > 1:
-            graph = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream(self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                snap = (state.clone(), finished.clone(), tokens.clone(), out.clone())
-                one_step()  # warm-up outside capture (lazy module loading); it only touched cache slot 0, rewritten below
-                state.copy_(snap[0]); finished.copy_(snap[1]); tokens.copy_(snap[2]); out.copy_(snap[3])
-                with torch.cuda.graph(graph, stream=side):
-                    one_step()
-            torch.cuda.current_stream(self.device).wait_stream(side)
-        n = 0
-        for t in range(max_new_tokens):
-            if graph is not None:
-                graph.replay()
-            else:
-                one_step()
-            n = t + 1
-            if eos_id >= 0 and (n % poll_every == 0 or n == max_new_tokens) and int(state[1].item()) == 0:
-                break
-        ids = out[:, :n]
-        if eos_id >= 0:  # HF stops as soon as every row has emitted EOS: trim to that length
-            is_eos = ids == eos_id
-            first = torch.where(is_eos.any(dim=1), is_eos.float().argmax(dim=1) + 1, torch.full((B,), n, device=self.device))
-            ids = ids[:, : int(first.max().item())]
+        B, vocab = inputs_embeds.shape[0], self.t5dims.vocab
         start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
+        if max_new_tokens <= 0:
+            return start
+        ids = self._t5_select_device(
+            inputs_embeds, attention_mask, max_new_tokens, eos_list(eos_id), pad_id, start_id,
+            lambda state, finished, tokens, out: (lambda lg: self._greedy_select(lg, B, vocab, state, finished, eos_id, pad_id, tokens, out)),
+            use_graph, poll_every, None)
         return torch.cat((start, ids), dim=1)
 
     def t5_greedy_lookup(self, inputs_embeds, attention_mask, text_ids, max_new_tokens, num_tokens=10, ngram=2, eos_id=1, pad_id=0, start_id=0):
@@ -1648,16 +1540,10 @@ class HipEngine:
             from .sampling import sample_loop
 
             ids = sample_loop(step, first, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
-            self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
-            if with_rules:
-                self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
         else:
             ids = beam_search(step, first[::num_beams].contiguous(), B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id,
                               early_stopping, num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
-            if sampler is not None:  # beam-search sampling
-                self.sample_stats = dict(path="host", steps=int(ids.shape[1]))
-            elif with_rules:
-                self.rules_stats = dict(path="host", steps=int(ids.shape[1]))
+        self._host_stats(ids, sampler, num_beams, with_rules)
         head = torch.full((ids.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
         return torch.cat((head, ids), dim=1)
 

@@ -360,6 +360,37 @@ def test_opt_greedy_with_rules_more_than_32_rows_run_in_chunks_of_32():
     assert torch.equal(ids[32:], eng.rules_decode_device(big[32:], big_am[32:], 4, **kw))
 
 
+def test_opt_greedy_sampling_and_rules_share_one_cached_decode_entry():
+    """greedy_decode, sample_decode_device and rules_decode_device run through one loop and one `_dec_cache` slot: calls of one shape replace
+    each other there, and greedy gives the same ids before, between and after them (= its eager ids).  Then the cached greedy entry is
+    replayed on OTHER inputs of the same shape (what the benchmark does every step): rows rolled by one, one row left-padded by two."""
+    eng, emb, am = _opt_prompt()
+    T = 8
+    kind = lambda: eng._dec_cache["key"][0]
+    eager = eng.greedy_decode(emb, am, T, eos_id=-1, use_graph=False)
+    first = eng.greedy_decode(emb, am, T, eos_id=-1, use_graph=True)
+    assert kind() == "greedy"
+    assert "argmax_out" not in eng._dec_cache  # the decode step's arg-max is the selection: no scratch buffers for it
+    eng.sample_decode_device(emb, am, T, eos_id=-1, top_k=1, use_graph=True)
+    assert kind() == "sample"
+    second = eng.greedy_decode(emb, am, T, eos_id=-1, use_graph=True)
+    assert kind() == "greedy"
+    eng.rules_decode_device(emb, am, T, eos_id=-1, repetition_penalty=1.5, use_graph=True)
+    assert kind() == "rules"
+    third = eng.greedy_decode(emb, am, T, eos_id=-1, use_graph=True)
+    assert kind() == "greedy"
+    assert eager.shape == (3, T)
+    for ids in (first, second, third):
+        assert torch.equal(ids, eager), (ids.tolist(), eager.tolist())
+    ent = eng._dec_cache
+    emb2, am2 = torch.roll(emb, 1, dims=0).contiguous(), am.clone()
+    am2[1, :2] = 0
+    replayed = eng.greedy_decode(emb2, am2, T, eos_id=-1, use_graph=True)
+    assert eng._dec_cache is ent and ent["graph"] is not None  # (the entry of `third`, replayed)
+    eager2 = eng.greedy_decode(emb2, am2, T, eos_id=-1, use_graph=False)
+    assert torch.equal(replayed, eager2), (replayed.tolist(), eager2.tolist())
+
+
 # ---- 5. the OPT engine: beam search -----------------------------------------------------------------------------------------------------
 class _BanEven:
     """a user LogitsProcessor: even token ids above 9 are forbidden"""
