@@ -513,6 +513,48 @@ def use_probes() -> None:
     _hip, HIP_LIB_PATH = lib, PROBES_LIB_PATH
 
 
+# ---- the companion libraries: shared libraries with their own exports, loaded on demand ----
+_companions = {}
+_i64, _i32, _sz = C.c_int64, C.c_int, C.c_size_t
+
+
+def _load_companion(path: str, version: int, declare) -> C.CDLL:
+    """Load a companion of libeilev_hip.so once (built next to it by build_hip()): `declare(sig)` gives every export its
+    sig(name, restype, *argtypes) and returns the name of the ABI version function.  No fallback: a missing build is an error."""
+    if path not in _companions:
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(path)
+
+        def sig(name, restype, *argtypes):
+            fn = getattr(lib, name)
+            fn.restype = restype
+            if argtypes:
+                fn.argtypes = list(argtypes)
+            return name
+
+        if getattr(lib, declare(sig))() != version:
+            raise RuntimeError(f"{path}: ABI version mismatch")
+        _companions[path] = lib
+    return _companions[path]
+
+
+def _fill_eos(params, eos_ids, limit: int, too_many: str):
+    """params.n_eos / params.eos from a list of at most `limit` ids."""
+    eos_ids = [int(e) for e in eos_ids]
+    if len(eos_ids) > limit:
+        raise NotImplementedError(too_many)
+    params.n_eos = len(eos_ids)
+    for i, e in enumerate(eos_ids):
+        params.eos[i] = e
+    return params
+
+
+def _row_vocab_supported(vocab: int, limit: int) -> bool:
+    """One workgroup holds the row in registers as 16-byte chunks: at most `limit` ids, a multiple of 4."""
+    return 0 < int(vocab) <= limit and int(vocab) % 4 == 0
+
+
 # ---- the prompt-lookup decoding companion library (include/eilev_pld.h): a second shared library with its own exports, loaded on demand ----
 PLD_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_pld.so")
 PLD_ABI_VERSION = 1
@@ -527,38 +569,20 @@ class PldParams(C.Structure):
 
 
 def pld_params(k, ngram, max_new, slot_base, slot_limit, corpus_cap, eos_ids) -> PldParams:
-    eos_ids = [int(e) for e in eos_ids]
-    if len(eos_ids) > PLD_MAX_EOS:
-        raise NotImplementedError(f"prompt lookup takes at most {PLD_MAX_EOS} EOS ids")
-    p = PldParams(int(k), int(ngram), int(max_new), int(slot_base), int(slot_limit), int(corpus_cap), len(eos_ids))
-    for i, e in enumerate(eos_ids):
-        p.eos[i] = e
-    return p
-
-
-_pld = None
+    p = PldParams(int(k), int(ngram), int(max_new), int(slot_base), int(slot_limit), int(corpus_cap))
+    return _fill_eos(p, eos_ids, PLD_MAX_EOS, f"prompt lookup takes at most {PLD_MAX_EOS} EOS ids")
 
 
 def load_pld() -> C.CDLL:
-    """Load libeilev_hip_pld.so (built next to libeilev_hip.so by build_hip()).  No fallback: a missing build is an error."""
-    global _pld
-    if _pld is None:
-        if not os.path.exists(PLD_LIB_PATH):
-            raise RuntimeError(f"{PLD_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(PLD_LIB_PATH)
-        i64, i32, sz = C.c_int64, C.c_int, C.c_size_t
+    """Load libeilev_hip_pld.so."""
+    def declare(sig):
         PP = C.POINTER(PldParams)
-        lib.eilev_pld_abi_version.restype = i32
-        lib.eilev_pld_scratch_bytes.restype = sz
-        lib.eilev_pld_scratch_bytes.argtypes = [i64, i64]
-        lib.eilev_pld_draft.restype = i32
-        lib.eilev_pld_draft.argtypes = [PP, vp, vp, vp, vp, vp]
-        lib.eilev_pld_step.restype = i32
-        lib.eilev_pld_step.argtypes = [PP, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        if lib.eilev_pld_abi_version() != PLD_ABI_VERSION:
-            raise RuntimeError(f"{PLD_LIB_PATH}: ABI version mismatch")
-        _pld = lib
-    return _pld
+        sig("eilev_pld_scratch_bytes", _sz, _i64, _i64)
+        sig("eilev_pld_draft", _i32, PP, vp, vp, vp, vp, vp)
+        sig("eilev_pld_step", _i32, PP, vp, _i64, _i64, vp, vp, vp, vp, vp, vp, vp, _sz, vp)
+        return sig("eilev_pld_abi_version", _i32)
+
+    return _load_companion(PLD_LIB_PATH, PLD_ABI_VERSION, declare)
 
 
 # ---- the device-sampling companion library (include/eilev_sample.h): a third shared library with its own exports, loaded on demand ----
@@ -577,41 +601,25 @@ class SampleParams(C.Structure):
 
 def sample_params(temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, min_new=0, max_new=1, eos_ids=(), pad_id=0, prefix_id=-1,
                   step_offset=0, finalize=1) -> SampleParams:
-    eos_ids = [int(e) for e in eos_ids]
-    if len(eos_ids) > SAMPLE_MAX_EOS:
-        raise NotImplementedError(f"device sampling takes at most {SAMPLE_MAX_EOS} EOS ids")
-    p = SampleParams(float(temperature), float(top_p), float(repetition_penalty), int(top_k or 0), int(min_new), int(max_new), len(eos_ids))
-    for i, e in enumerate(eos_ids):
-        p.eos[i] = e
+    p = SampleParams(float(temperature), float(top_p), float(repetition_penalty), int(top_k or 0), int(min_new), int(max_new))
+    _fill_eos(p, eos_ids, SAMPLE_MAX_EOS, f"device sampling takes at most {SAMPLE_MAX_EOS} EOS ids")
     p.pad_id, p.prefix_id, p.step_offset, p.finalize = int(pad_id), int(prefix_id), int(step_offset), int(finalize)
     return p
 
 
 def sample_supported(vocab: int) -> bool:
     """The vocabulary sizes eilev_sample_select takes (anything else returns EILEV_E_UNSUPPORTED)."""
-    return 0 < int(vocab) <= SAMPLE_MAX_VOCAB and int(vocab) % 4 == 0
-
-
-_sample = None
+    return _row_vocab_supported(vocab, SAMPLE_MAX_VOCAB)
 
 
 def load_sample() -> C.CDLL:
-    """Load libeilev_hip_sample.so (built next to libeilev_hip.so by build_hip()).  No fallback: a missing build is an error."""
-    global _sample
-    if _sample is None:
-        if not os.path.exists(SAMPLE_LIB_PATH):
-            raise RuntimeError(f"{SAMPLE_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(SAMPLE_LIB_PATH)
-        i64, i32, sz = C.c_int64, C.c_int, C.c_size_t
-        lib.eilev_sample_abi_version.restype = i32
-        lib.eilev_sample_scratch_bytes.restype = sz
-        lib.eilev_sample_scratch_bytes.argtypes = [i64, i64]
-        lib.eilev_sample_select.restype = i32
-        lib.eilev_sample_select.argtypes = [C.POINTER(SampleParams), vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        if lib.eilev_sample_abi_version() != SAMPLE_ABI_VERSION:
-            raise RuntimeError(f"{SAMPLE_LIB_PATH}: ABI version mismatch")
-        _sample = lib
-    return _sample
+    """Load libeilev_hip_sample.so."""
+    def declare(sig):
+        sig("eilev_sample_scratch_bytes", _sz, _i64, _i64)
+        sig("eilev_sample_select", _i32, C.POINTER(SampleParams), vp, _i64, _i64, vp, vp, vp, vp, vp, vp, vp, _sz, vp)
+        return sig("eilev_sample_abi_version", _i32)
+
+    return _load_companion(SAMPLE_LIB_PATH, SAMPLE_ABI_VERSION, declare)
 
 
 # ---- the logits-rules companion library (include/eilev_rules.h): a fourth shared library with its own exports, loaded on demand ----
@@ -631,46 +639,28 @@ class RulesParams(C.Structure):
 
 def rules_params(repetition_penalty=1.0, no_repeat_ngram=0, min_new=0, max_new=1, eos_ids=(), pad_id=0, prefix_id=-1, step_offset=0,
                  finalize=1) -> RulesParams:
-    eos_ids = [int(e) for e in eos_ids]
-    if len(eos_ids) > RULES_MAX_EOS:
-        raise NotImplementedError(f"the device rules take at most {RULES_MAX_EOS} EOS ids")
-    p = RulesParams(float(repetition_penalty), int(no_repeat_ngram or 0), int(min_new), int(max_new), len(eos_ids))
-    for i, e in enumerate(eos_ids):
-        p.eos[i] = e
+    p = RulesParams(float(repetition_penalty), int(no_repeat_ngram or 0), int(min_new), int(max_new))
+    _fill_eos(p, eos_ids, RULES_MAX_EOS, f"the device rules take at most {RULES_MAX_EOS} EOS ids")
     p.pad_id, p.prefix_id, p.step_offset, p.finalize = int(pad_id), int(prefix_id), int(step_offset), int(finalize)
     return p
 
 
 def rules_supported(vocab: int) -> bool:
     """The vocabulary sizes the eilev_rules_* calls take (anything else returns EILEV_E_UNSUPPORTED)."""
-    return 0 < int(vocab) <= RULES_MAX_VOCAB and int(vocab) % 4 == 0
-
-
-_rules = None
+    return _row_vocab_supported(vocab, RULES_MAX_VOCAB)
 
 
 def load_rules() -> C.CDLL:
-    """Load libeilev_hip_rules.so (built next to libeilev_hip.so by build_hip()).  No fallback: a missing build is an error."""
-    global _rules
-    if _rules is None:
-        if not os.path.exists(RULES_LIB_PATH):
-            raise RuntimeError(f"{RULES_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(RULES_LIB_PATH)
-        i64, i32, sz = C.c_int64, C.c_int, C.c_size_t
+    """Load libeilev_hip_rules.so."""
+    def declare(sig):
         PP = C.POINTER(RulesParams)
-        lib.eilev_rules_abi_version.restype = i32
-        lib.eilev_rules_scratch_bytes.restype = sz
-        lib.eilev_rules_scratch_bytes.argtypes = [i64, i64]
-        lib.eilev_rules_select.restype = i32
-        lib.eilev_rules_select.argtypes = [PP, vp, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]
-        lib.eilev_rules_topk_logprob.restype = i32
-        lib.eilev_rules_topk_logprob.argtypes = [PP, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]
-        lib.eilev_rules_ban.restype = i32
-        lib.eilev_rules_ban.argtypes = [PP, vp, i64, i64, vp, vp, vp]
-        if lib.eilev_rules_abi_version() != RULES_ABI_VERSION:
-            raise RuntimeError(f"{RULES_LIB_PATH}: ABI version mismatch")
-        _rules = lib
-    return _rules
+        sig("eilev_rules_scratch_bytes", _sz, _i64, _i64)
+        sig("eilev_rules_select", _i32, PP, vp, _i64, _i64, vp, vp, vp, vp, vp, vp, _sz, vp)
+        sig("eilev_rules_topk_logprob", _i32, PP, vp, vp, _i64, _i64, _i64, vp, vp, vp, vp, vp, vp, _sz, vp)
+        sig("eilev_rules_ban", _i32, PP, vp, _i64, _i64, vp, vp, vp)
+        return sig("eilev_rules_abi_version", _i32)
+
+    return _load_companion(RULES_LIB_PATH, RULES_ABI_VERSION, declare)
 
 
 def check(rc: int, what: str) -> None:

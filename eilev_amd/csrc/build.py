@@ -9,22 +9,20 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["gemm.hip", "gemm_pp4_ext.hip", "norm.hip", "attention.hip", "misc.hip", "attn_decode.hip", "vision.hip", "opt.hip", "t5.hip", "blocks.hip", "backward.hip", "comm.hip", "gemv.hip"]
-HEADERS = ["common.h", "stages.h", "gemm_common.h", "gemm_tiled.h", "gemm_pp4.h", "gemm_w6.h", "gemm_skinny.h", "attn_frame3.h", os.path.join("..", "..", "include", "eilev.h")]
+HEADERS = ["common.h", "row_select.h", "stages.h", "gemm_common.h", "gemm_tiled.h", "gemm_pp4.h", "gemm_w6.h", "gemm_skinny.h", "attn_frame3.h", os.path.join("..", "..", "include", "eilev.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"]
 LIB = os.path.join(HERE, "libeilev_hip.so")
-# the prompt-lookup decoding companion (include/eilev_pld.h): its own source, header and version script; it does not link the core library
-PLD_SOURCE = "pld.hip"
-PLD_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_pld.h")]
-PLD_LIB = os.path.join(HERE, "libeilev_hip_pld.so")
-# the device-sampling companion (include/eilev_sample.h), built the same way
-SAMPLE_SOURCE = "sample.hip"
-SAMPLE_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_sample.h")]
-SAMPLE_LIB = os.path.join(HERE, "libeilev_hip_sample.so")
-# the logits-rules companion (include/eilev_rules.h), built the same way
-RULES_SOURCE = "rules.hip"
-RULES_HEADERS = ["common.h", os.path.join("..", "..", "include", "eilev.h"), os.path.join("..", "..", "include", "eilev_rules.h")]
-RULES_LIB = os.path.join(HERE, "libeilev_hip_rules.so")
+# The companion libraries: each its own source, public header and version script; none links the core library.  row_select.h is the device
+# code that sample.hip and rules.hip share with misc.hip.
+_INC = os.path.join("..", "..", "include")
+COMPANIONS = [  # (source, headers, export map, output)
+    ("pld.hip", ["common.h", os.path.join(_INC, "eilev.h"), os.path.join(_INC, "eilev_pld.h")], "exports_pld.map", "libeilev_hip_pld.so"),
+    ("sample.hip", ["common.h", "row_select.h", os.path.join(_INC, "eilev.h"), os.path.join(_INC, "eilev_sample.h")], "exports_sample.map",
+     "libeilev_hip_sample.so"),
+    ("rules.hip", ["common.h", "row_select.h", os.path.join(_INC, "eilev.h"), os.path.join(_INC, "eilev_rules.h")], "exports_rules.map",
+     "libeilev_hip_rules.so"),
+]
 
 
 def _hipcc() -> str:
@@ -69,13 +67,12 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "", ext
 
     # the default build (no variant) also builds the companion libraries; the probe variant does not need them
     side_jobs = []
-    for src, hdr, emap, out in ((PLD_SOURCE, PLD_HEADERS, "exports_pld.map", PLD_LIB), (SAMPLE_SOURCE, SAMPLE_HEADERS, "exports_sample.map", SAMPLE_LIB),
-                                (RULES_SOURCE, RULES_HEADERS, "exports_rules.map", RULES_LIB)):
-        src, emap = os.path.join(HERE, src), os.path.join(HERE, emap)
+    for src, hdr, emap, out in COMPANIONS:
+        src, emap, out = os.path.join(HERE, src), os.path.join(HERE, emap), os.path.join(HERE, out)
         if not variant and (force or _stale(out, [src, emap] + [os.path.join(HERE, h) for h in hdr])):
             side_jobs.append([_hipcc(), *FLAGS, *extra_flags, "-shared", "-o", out, src, "-Wl,--version-script=" + emap])
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES) + 3) as ex:
+    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(COMPANIONS)) as ex:
         side_futs = [ex.submit(run, j) for j in side_jobs]
         for warn in ex.map(run, jobs):
             if verbose and warn.strip():

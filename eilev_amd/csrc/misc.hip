@@ -1,6 +1,6 @@
 // misc.hip — the HBM-bound glue kernels of the path: patch gather (im2col), embedding gather/scatter,
 // OPT position ids, KV-cache writes, greedy selection.  (Single-query decode attention: attn_decode.hip.)
-#include "common.h"
+#include "row_select.h"
 
 namespace {
 
@@ -328,97 +328,17 @@ __global__ __launch_bounds__(1024) void topk_logprob_kernel(const float *__restr
     __shared__ int wi[16];
     __shared__ float bcast[2];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const float4 *l4 = reinterpret_cast<const float4 *>(logits + (int64_t)row * vocab);
     const int n4 = vocab >> 2;
-    // the thread's <= 16 chunks of 16 bytes (chunk j = float4 index tid + 1024 j) stay in registers: every later pass is VALU only
-    float4 e[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) e[j] = tid + 1024 * j < n4 ? l4[tid + 1024 * j] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    // ---- row maximum
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) mx = fmaxf(fmaxf(mx, fmaxf(e[j].x, e[j].y)), fmaxf(e[j].z, e[j].w));
-    mx = wave_max(mx);
-    if (lane == 0) wv[wid] = mx;
-    __syncthreads();
-    if (tid == 0) {
-        float m = wv[0];
-        for (int w = 1; w < 16; ++w) m = fmaxf(m, wv[w]);
-        bcast[0] = m;
-    }
-    __syncthreads();
-    mx = bcast[0];
-    // ---- sum of exp(x - max) (padding entries are -inf: exp = 0)
-    float sm = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (tid + 1024 * j < n4) sm += (expf(e[j].x - mx) + expf(e[j].y - mx)) + (expf(e[j].z - mx) + expf(e[j].w - mx));
-    sm = wave_sum(sm);
-    __syncthreads();  // (wv is reused)
-    if (lane == 0) wv[wid] = sm;
-    __syncthreads();
-    if (tid == 0) {
-        float t = 0.0f;
-        for (int w = 0; w < 16; ++w) t += wv[w];
-        bcast[1] = logf(t);
-    }
-    __syncthreads();
-    const float lg = bcast[1], sc = row_score ? row_score[row] : 0.0f;
-    // ---- `keep` rounds of arg-max; `taken`: bit (j * 4 + u) = element u of chunk j already won
-    unsigned long long taken = 0;
-    float best;
-    int bi;
-    auto rescan = [&]() {
-        best = -INFINITY;
-        bi = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float ev[4] = {e[j].x, e[j].y, e[j].z, e[j].w};
-            const int i = tid + 1024 * j;
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i < n4 && !((taken >> (j * 4 + u)) & 1ull) && (ev[u] > best || (ev[u] == best && i * 4 + u < bi))) {
-                    best = ev[u];
-                    bi = i * 4 + u;
-                }
-        }
-    };
-    rescan();
-    for (int k = 0; k < keep; ++k) {
-        float b = best;
-        int ix = bi;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(b, o, 64);
-            const int oi = __shfl_xor(ix, o, 64);
-            if (ov > b || (ov == b && oi < ix)) {
-                b = ov;
-                ix = oi;
-            }
-        }
-        __syncthreads();  // (the previous round's wv / wi have been read)
-        if (lane == 0) {
-            wv[wid] = b;
-            wi[wid] = ix;
-        }
-        __syncthreads();
-        b = wv[0];
-        ix = wi[0];
-#pragma unroll
-        for (int w = 1; w < 16; ++w)
-            if (wv[w] > b || (wv[w] == b && wi[w] < ix)) {
-                b = wv[w];
-                ix = wi[w];
-            }
-        if (tid == 0) {
-            out_val[(int64_t)row * keep + k] = ((b - mx) - lg) + sc;
-            out_idx[(int64_t)row * keep + k] = ix == 0x7fffffff ? 0 : ix;
-        }
-        if (ix != 0x7fffffff && ((ix >> 2) & 1023) == tid) {  // this thread owned the winner: chunk j = (ix / 4) / 1024, element ix % 4
-            taken |= 1ull << ((((ix >> 2) >> 10) << 2) + (ix & 3));
-            rescan();
-        }
-    }
+    float4 e[kChunks];
+    load_row(e, logits + (int64_t)row * vocab, n4, tid);
+    float mx, lg;
+    row_log_softmax(e, n4, wv, bcast, tid, lane, wid, mx, lg);
+    const float sc = row_score ? row_score[row] : 0.0f;
+    // the rounds compare the logits themselves; the log-probability of a winner is formed when it is written
+    topk_rounds(e, n4, keep, wv, wi, tid, lane, wid, [&](int k, float v, int ix) {
+        out_val[(int64_t)row * keep + k] = ((v - mx) - lg) + sc;
+        out_idx[(int64_t)row * keep + k] = ix;
+    });
 }
 
 // ---- beam search bookkeeping of one step (include/eilev.h eilev_beam_advance; oracle/eilev_ref.c holds the plain restatement).  One

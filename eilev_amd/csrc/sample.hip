@@ -1,24 +1,22 @@
 // sample.hip — multinomial sampling on the device (include/eilev_sample.h): repetition penalty, minimum length, temperature, top-k,
-// top-p and the draw of one decode step, one 1024-thread workgroup per row.  Standalone library (libeilev_hip_sample.so): it shares
-// common.h's macros with the core library and nothing else.
+// top-p and the draw of one decode step, one 1024-thread workgroup per row.  Standalone library (libeilev_hip_sample.so): it links
+// nothing of the core library.  The row in registers, the penalty / ban tables, the rules on the chunks and the commit of the token are
+// row_select.h's, shared with rules.hip and misc.hip; this file holds the two thresholds and the draw.
 //
-// The row's <= 16 chunks of 16 bytes stay in registers (as in misc.hip topk_logprob_kernel); every pass after the load is VALU + LDS.
 // Both thresholds are the same question — "keep x while the weight of the elements strictly above x is below Q" (top-k: weight 1,
 // Q = k; top-p: weight = probability, Q = top_p * total) — answered by one radix select over 256-bin histograms in LDS.  Probabilities are
 // 40-bit fixed point summed in 64-bit integers: the sums do not depend on the order of the LDS atomics, so the result is reproducible.
 #include <climits>
 
-#include "common.h"
+#include "row_select.h"
 #include "../../include/eilev_sample.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kThreads = 1024;
-constexpr int kChunks = 16;                        // float4 chunks per thread: 1024 * 16 * 4 = 65536 = EILEV_SAMPLE_MAX_VOCAB
-constexpr int kBits = EILEV_SAMPLE_MAX_VOCAB / 32;  // words of a one-bit-per-id table
-constexpr float kScale = 1099511627776.0f;          // 2^40
+static_assert(EILEV_SAMPLE_MAX_VOCAB == kMaxVocab && EILEV_SAMPLE_MAX_EOS == kMaxEos, "include/eilev_sample.h and row_select.h disagree");
+constexpr float kScale = 1099511627776.0f;  // 2^40
 
 struct SelState {
     u64 hw[256];  // weight histogram of the current level; bin 0 holds the largest values
@@ -167,50 +165,11 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(EilevSampleParams p, c
     const int64_t step = (int64_t)state[0] + p.step_offset;
     const bool step_ok = step >= 0 && step < p.max_new;
 
-    // ---- one bit per id: the row's history (repetition penalty) and the banned EOS ids (min_new)
-    for (int i = tid; i < kBits; i += kThreads) {
-        pen_bits[i] = 0;
-        ban_bits[i] = 0;
-    }
-    __syncthreads();
-    if (p.repetition_penalty != 1.0f) {
-        if (tid == 0 && p.prefix_id >= 0 && p.prefix_id < vocab) atomicOr(&pen_bits[p.prefix_id >> 5], 1u << (p.prefix_id & 31));
-        const int64_t nh = step < 0 ? 0 : (step < p.max_new ? step : p.max_new);
-        for (int64_t i = tid; i < nh; i += kThreads) {
-            const int64_t id = out_tokens[(int64_t)b * p.max_new + i];
-            if (id >= 0 && id < vocab) atomicOr(&pen_bits[id >> 5], 1u << (id & 31));
-        }
-    }
-    if (step < p.min_new) {
-#pragma unroll
-        for (int k = 0; k < EILEV_SAMPLE_MAX_EOS; ++k)
-            if (tid == k && k < p.n_eos && p.eos[k] >= 0 && p.eos[k] < vocab) atomicOr(&ban_bits[p.eos[k] >> 5], 1u << (p.eos[k] & 31));
-    }
-    __syncthreads();
-
-    // ---- load, steps 1 - 3
-    const float4 *l4 = reinterpret_cast<const float4 *>(logits + (int64_t)b * vocab);
-    const float4 ninf4 = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    // ---- one bit per id: the row's history (repetition penalty) and the banned EOS ids (min_new); load, steps 1 - 3
+    fill_tables(p, out_tokens + (int64_t)b * p.max_new, step, 0, vocab, tid, pen_bits, ban_bits);
     float4 e[kChunks];
-#pragma unroll
-    for (int j = 0; j < kChunks; ++j) e[j] = tid + kThreads * j < n4 ? l4[tid + kThreads * j] : ninf4;
-    const float pen = p.repetition_penalty, temp = p.temperature;
-#pragma unroll
-    for (int j = 0; j < kChunks; ++j) {
-        const int id0 = (tid + kThreads * j) * 4;  // a multiple of 4: the chunk's four bits share a word
-        const uint32_t pb = (pen_bits[(id0 >> 5) & (kBits - 1)] >> (id0 & 31)) & 15u, bb = (ban_bits[(id0 >> 5) & (kBits - 1)] >> (id0 & 31)) & 15u;
-        float ev[4] = {e[j].x, e[j].y, e[j].z, e[j].w};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float x = ev[u];
-            if (x != x) x = -INFINITY;
-            if ((pb >> u) & 1u) x = x < 0.0f ? x * pen : x / pen;
-            if ((bb >> u) & 1u) x = -INFINITY;
-            if (temp != 1.0f) x = x / temp;
-            ev[u] = x + 0.0f;  // -0 -> +0: equal values have equal integer images
-        }
-        e[j] = make_float4(ev[0], ev[1], ev[2], ev[3]);
-    }
+    load_row(e, logits + (int64_t)b * vocab, n4, tid);
+    apply_rules(e, pen_bits, ban_bits, p.repetition_penalty, p.temperature, tid);
 
     // ---- row maximum, and minimum over the finite entries
     float mx = -INFINITY, mn = INFINITY;
@@ -253,12 +212,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(EilevSampleParams p, c
             for (int j = 0; j < kChunks; ++j) e[j] = mask_below(e[j], thr);
         }
     }
-    if (warped) {
-        float4 *w4 = reinterpret_cast<float4 *>(warped + (int64_t)b * vocab);
-#pragma unroll
-        for (int j = 0; j < kChunks; ++j)
-            if (tid + kThreads * j < n4) w4[tid + kThreads * j] = e[j];
-    }
+    if (warped) store_row(e, warped + (int64_t)b * vocab, n4, tid);
 
     // ---- step 6: the weight of every 4096-id chunk, the chunk that holds u * total, then a scan inside that chunk
 #pragma unroll
@@ -313,30 +267,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(EilevSampleParams p, c
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        const int64_t drawn = draw_tok >= 0 ? draw_tok : 0;
-        const bool was = finished[b] != 0;
-        const int64_t tok = was ? p.pad_id : drawn;
-        bool eos = false;
-        for (int k = 0; k < EILEV_SAMPLE_MAX_EOS; ++k) eos = eos || (k < p.n_eos && p.eos[k] >= 0 && tok == p.eos[k]);
-        tokens[b] = tok;
-        if (step_ok) out_tokens[(int64_t)b * p.max_new + step] = tok;
-        if (eos && !was) finished[b] = 1;
-        if (whole_step) {
-            if (p.finalize) state[0] = (int32_t)(step + 1);
-            state[1] = (was || eos) ? 0 : 1;
-        }
-    }
-}
-
-// rows > 1: the step counter and the "any row unfinished" word, after every row's workgroup
-__global__ void sample_finalize_kernel(int32_t *__restrict__ state, const uint8_t *__restrict__ finished, int rows, int step_offset, int finalize) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        int unf = 0;
-        for (int b = 0; b < rows; ++b) unf |= finished[b] ? 0 : 1;
-        if (finalize) state[0] = state[0] + step_offset + 1;
-        state[1] = unf;
-    }
+    if (tid == 0) commit_token(p, draw_tok >= 0 ? draw_tok : 0, b, step, state, finished, tokens, out_tokens, whole_step);
 }
 
 }  // namespace
@@ -366,7 +297,7 @@ extern "C" int eilev_sample_select(const EilevSampleParams *p, const float *logi
                        out_tokens, warped, rows == 1 ? 1 : 0);
     EILEV_LAUNCH_CHECK();
     if (rows == 1) return EILEV_OK;  // (the single workgroup finished the step itself)
-    hipLaunchKernelGGL(sample_finalize_kernel, dim3(1), dim3(64), 0, s, state, (const uint8_t *)finished, (int)rows, (int)p->step_offset,
+    hipLaunchKernelGGL(row_finalize_kernel<>, dim3(1), dim3(64), 0, s, state, (const uint8_t *)finished, (int)rows, (int)p->step_offset,
                        (int)p->finalize);
     EILEV_LAUNCH_CHECK();
     return EILEV_OK;

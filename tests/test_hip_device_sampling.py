@@ -176,6 +176,55 @@ def test_step_offset_and_finalize(rows):
     assert a["state"] == [3, 1] and b["state"] == [3, 1]
 
 
+@pytest.mark.parametrize("vocab", [1000, 50272])
+@pytest.mark.parametrize("rows", [1, 7])
+def test_sample_select_and_rules_select_share_their_steps(rows, vocab):
+    """The steps the two kernels share (csrc/row_select.h: tables, rules on the row, commit of the token, finalize), pinned to each other:
+    sampling with top_k = 1, top_p = 1, temperature = 1 and u = 0 draws the arg-max after the rules, which is what eilev_rules_select
+    with no n-gram ban takes.  tokens, out_tokens, finished and state must be equal."""
+    rl = abi.load_rules()
+    max_new, min_new, pen, pad = 12, 7, 1.5, 1
+    logits = _logits(rows, vocab)
+    top = logits.topk(3, dim=1).indices
+    best, second = top[:, 0], top[:, 1]
+    low = logits.argmin(dim=1)
+    out = torch.full((rows, max_new), -7, dtype=torch.int64)  # duplicates, ids of both signs, one id outside the vocabulary
+    hist = (best, torch.full_like(best, 3), second, best, torch.full_like(best, vocab + 5), torch.full_like(best, 3), low, second)
+    out[:, :len(hist)] = torch.stack(hist, dim=1)
+    prefix = int(top[0, 2])
+    free = SampleSpec(1.0, 1, 1.0, repetition_penalty=pen, pad_id=pad, prefix_id=prefix)
+    # the first EOS id is row 0's arg-max after the penalty: banned below min_new (another id wins), taken above it (the row finishes)
+    eos = (int(processed_scores(logits, row_history(out, min_new, prefix), free, min_new)[0].argmax()), 5)
+    spec = SampleSpec(1.0, 1, 1.0, repetition_penalty=pen, min_new=min_new, eos=eos, pad_id=pad, prefix_id=prefix)
+    uni = torch.zeros((max_new, rows))
+    fins = [torch.zeros(rows, dtype=torch.uint8)]
+    fins[0][rows // 2] = 1  # one row has finished (rows = 1: that row, and the call with it unfinished as well)
+    if rows == 1:
+        fins.append(torch.zeros(rows, dtype=torch.uint8))
+    # (state[0], step_offset, finalize): step 5 is below min_new, step 7 is not
+    for state0, step_offset, finalize in ((5, 0, 1), (8, -1, 0)):
+        step = state0 + step_offset
+        scores = processed_scores(logits, row_history(out, step, prefix), spec, step)
+        top2 = scores.topk(2, dim=1).values
+        assert bool((top2[:, 0] > top2[:, 1]).all())  # the arg-max after the rules is unique: both kernels must find it
+        for fin in fins:
+            tok = torch.zeros(rows, dtype=torch.int64)
+            rc, got = _select(logits, uni, [state0, 1], fin, tok, out, spec, step_offset, finalize, want_warped=False)
+            assert rc == 0, rc
+            dv = lambda a, dt: torch.as_tensor(a).to(dt).cuda().contiguous()
+            lg, st, f, t, o = dv(logits, torch.float32), dv([state0, 1], torch.int32), dv(fin, torch.uint8), dv(tok, torch.int64), dv(out, torch.int64)
+            prm = abi.rules_params(pen, 0, min_new, max_new, eos, pad, prefix, step_offset, finalize)
+            rc = rl.eilev_rules_select(C.byref(prm), P(lg), rows, vocab, P(st), P(f), P(t), P(o), None, None, 0, stream_ptr())
+            torch.cuda.synchronize()
+            assert rc == 0, rc
+            assert torch.equal(got["tokens"], t.cpu()) and torch.equal(got["out"], o.cpu())
+            assert torch.equal(got["finished"], f.cpu()) and got["state"] == st.cpu().tolist()
+            live = ~fin.bool()
+            assert torch.equal(got["tokens"][live], scores.argmax(dim=1)[live]) and bool((got["tokens"][~live] == pad).all())
+            if live[0]:
+                assert (int(got["tokens"][0]) == eos[0]) == (step >= min_new) and int(got["finished"][0]) == int(step >= min_new)
+
+
 def test_grid_uniforms_give_the_distribution():
     """4096 draws of ONE row as 128 calls of 32 rows with u_j = (j + 0.5) / 4096: every id is drawn 4096 p_i times, +-1."""
     vocab, calls, R = 1000, 128, 32
