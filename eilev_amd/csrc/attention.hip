@@ -20,6 +20,12 @@
 int g_attn_force_v1 = 0, g_attn_dbg = 0;
 #ifdef EILEV_PROBES
 extern "C" int eilev_debug_attn_v1(int on) { g_attn_force_v1 = on & 1; g_attn_dbg = on >> 1; return 0; }
+// the kernel instance launch_attention chose last (eilev_debug_attention reports it): v1<DP> = DP, v2<NWQ, DB, REL> = 1000 + 100 NWQ + 10 DB + REL,
+// attn_frame_kernel = 2000, attn_frame3_kernel = 2003 (its HM form 2004), the dropout form of v1<DP> = 3000 + DP; 0 = nothing launched
+static int g_attn_form = 0;
+#define ATTN_FORM(code) (g_attn_form = (code))
+#else
+#define ATTN_FORM(code) ((void)0)
 #endif
 
 namespace {
@@ -810,6 +816,7 @@ int launch_attn_v2(const AttnArgs &a, hipStream_t s) {
 int launch_attention(const AttnArgs &a_in, hipStream_t s) {
     AttnArgs a = a_in;
     a.dbg = g_attn_dbg;
+    ATTN_FORM(0);
     if (a.batch <= 0 || a.sq <= 0) return EILEV_OK;
     if (!a.q || !a.k || !a.v || !a.o || a.skv <= 0) return EILEV_E_BADARG;
     if ((a.hd & 7) || a.hd > 128 || (a.ldq & 7) || (a.ldk & 7) || (a.ldv & 7) || (a.ldo & 7) || ((uintptr_t)a.o & 15) || (a.q_hs & 7) ||
@@ -819,7 +826,7 @@ int launch_attention(const AttnArgs &a_in, hipStream_t s) {
         if (a.hd != 88 || a.sq != 257 || a.skv != 257 || a.causal || a.key_mask || a.rel_tab || a.drop_thr || (a.q_hs & 7) || (a.q_bs & 7) ||
             a.q_hs != a.k_hs || a.q_hs != a.v_hs || (int64_t)a.sq * a.hd * 2 >= 0x7fff0000ll)
             return EILEV_E_UNSUPPORTED;
-        return launch_attn_frame3<88, 17, true>(a, s);
+        return (ATTN_FORM(2004), launch_attn_frame3<88, 17, true>(a, s));
     }
     // whole-frame ViT attention: S = 257 (17 tiles of 16), hd = 88, no mask, q / k / v rows of one fused buffer
     if (!g_attn_force_v1 && !(a.dbg & DBG_ATTN_NO_FRAME) && !a.rel_tab && !a.drop_thr && a.hd == 88 && a.sq == a.skv && a.sq > 256 && a.sq <= 272 && !a.causal && !a.key_mask &&
@@ -835,33 +842,34 @@ int launch_attention(const AttnArgs &a_in, hipStream_t s) {
             a.v = a.q + 2 * (int64_t)a.sq * a.heads * a.hd;
         }
 #endif
-        if (a.sq == 257 && !(a.dbg & DBG_ATTN_NO_FRAME3) && ((a.dbg & (DBG_ATTN_FRAME3 | DBG_ATTN_FRAME3_STAMPS)) || a.batch >= 512)) return launch_attn_frame3<88, 17>(a, s);
-        return launch_attn_frame<88, 17>(a, s);
+        if (a.sq == 257 && !(a.dbg & DBG_ATTN_NO_FRAME3) && ((a.dbg & (DBG_ATTN_FRAME3 | DBG_ATTN_FRAME3_STAMPS)) || a.batch >= 512)) return (ATTN_FORM(2003), launch_attn_frame3<88, 17>(a, s));
+        return (ATTN_FORM(2000), launch_attn_frame<88, 17>(a, s));
     }
     // hd = 64 with >= 128 query rows (the flan-t5 encoder: L = 960, relative position bias; also its bias-free long forms): round 5
     // (its bias lookup does not clamp: the table must cover every distance of the launch, key - query - (skv - sq) in [-(skv - 1), sq - 1])
     if (!g_attn_force_v1 && !a.drop_thr && a.hd == 64 && a.sq >= 128 && a.skv >= 64 && a.scale > 0.0f &&
         (!a.rel_tab || (a.rel_n <= ATTN_V2_REL_MAX && a.rel_off >= a.skv - 1 && a.rel_off + a.sq <= a.rel_n))) {
         const int qt = (a.sq + 31) / 32;
-        if (a.rel_tab) return qt >= 5 ? launch_attn_v2<8, 2, true>(a, s) : launch_attn_v2<4, 2, true>(a, s);
-        return qt >= 5 ? launch_attn_v2<8, 2, false>(a, s) : launch_attn_v2<4, 2, false>(a, s);
+        if (a.rel_tab) return qt >= 5 ? (ATTN_FORM(1821), launch_attn_v2<8, 2, true>(a, s)) : (ATTN_FORM(1421), launch_attn_v2<4, 2, true>(a, s));
+        return qt >= 5 ? (ATTN_FORM(1820), launch_attn_v2<8, 2, false>(a, s)) : (ATTN_FORM(1420), launch_attn_v2<4, 2, false>(a, s));
     }
     // hd = 128 (OPT-6.7B prefill), >= 64 query rows: round 6
     if (!g_attn_force_v1 && !a.rel_tab && !a.drop_thr && a.hd == 128 && a.sq >= 64 && a.skv >= 64) {
         const int qt = (a.sq + 31) / 32;
 #ifdef EILEV_PROBES
-        if (a.dbg & DBG_ATTN_V2_4WAVES) return launch_attn_v2<4, 4>(a, s);  // probe: 4 waves per workgroup (512 registers per wave, two blocks in flight)
+        if (a.dbg & DBG_ATTN_V2_4WAVES) return (ATTN_FORM(1440), launch_attn_v2<4, 4>(a, s));  // probe: 4 waves per workgroup (512 registers per wave, two blocks in flight)
 #endif
-        return qt >= 5 ? launch_attn_v2<8, 4>(a, s) : launch_attn_v2<4, 4>(a, s);
+        return qt >= 5 ? (ATTN_FORM(1840), launch_attn_v2<8, 4>(a, s)) : (ATTN_FORM(1440), launch_attn_v2<4, 4>(a, s));
     }
     if (!g_attn_force_v1 && !a.rel_tab && !a.drop_thr && (a.hd == 80 || a.hd == 88 || a.hd == 72) && a.skv >= 32) {
         const int qt = (a.sq + 31) / 32;
-        if (qt == 9 || qt > 16) return (qt == 9) ? launch_attn_v2<9>(a, s) : launch_attn_v2<8>(a, s);
-        if (qt >= 5) return launch_attn_v2<8>(a, s);
-        if (qt >= 3) return launch_attn_v2<4>(a, s);
-        return launch_attn_v2<2>(a, s);
+        if (qt == 9 || qt > 16) return (qt == 9) ? (ATTN_FORM(1930), launch_attn_v2<9>(a, s)) : (ATTN_FORM(1830), launch_attn_v2<8>(a, s));
+        if (qt >= 5) return (ATTN_FORM(1830), launch_attn_v2<8>(a, s));
+        if (qt >= 3) return (ATTN_FORM(1430), launch_attn_v2<4>(a, s));
+        return (ATTN_FORM(1230), launch_attn_v2<2>(a, s));
     }
     const dim3 grid((a.sq + 63) / 64, a.heads, a.batch), block(256);
+    ATTN_FORM((a.drop_thr ? 3000 : 0) + (a.hd <= 64 ? 64 : a.hd <= 96 ? 96 : 128));
     if (a.drop_thr) {
         if (a.hd <= 64) hipLaunchKernelGGL((attn_prefill_kernel<64, true>), grid, block, 0, s, a);
         else if (a.hd <= 96) hipLaunchKernelGGL((attn_prefill_kernel<96, true>), grid, block, 0, s, a);
@@ -872,3 +880,39 @@ int launch_attention(const AttnArgs &a_in, hipStream_t s) {
     EILEV_LAUNCH_CHECK();
     return EILEV_OK;
 }
+
+#ifdef EILEV_PROBES
+// probe / test entry (tests/test_hip_attn_prefill.py): ONE launch_attention on the caller's buffers.  The struct is AttnArgs field by field
+// as plain pointers and integers, without hm and dropout (the ctypes mirror lives with the tests); struct_bytes must be its size, so a
+// stale mirror is refused instead of run.  *form receives the code of the kernel instance that was launched (ATTN_FORM above).
+struct EilevDebugAttnArgs {
+    const void *q, *k, *v;
+    void *o;
+    int64_t q_bs, k_bs, v_bs, o_bs;
+    int64_t q_hs, k_hs, v_hs, o_hs;
+    int64_t ldq, ldk, ldv, ldo;
+    int32_t batch, heads, sq, skv, hd;
+    float scale;
+    int32_t causal, pad0;
+    const int32_t *key_mask;
+    int64_t mask_ld;
+    const float *rel_tab;
+    int64_t rel_hs;
+    int32_t rel_off, rel_n;
+};
+extern "C" int eilev_debug_attention(const EilevDebugAttnArgs *args, size_t struct_bytes, int *form, void *stream) {
+    if (!args || struct_bytes != sizeof(EilevDebugAttnArgs)) return EILEV_E_BADARG;
+    AttnArgs a;
+    a.q = (const bf16 *)args->q; a.k = (const bf16 *)args->k; a.v = (const bf16 *)args->v; a.o = (bf16 *)args->o;
+    a.q_bs = args->q_bs; a.k_bs = args->k_bs; a.v_bs = args->v_bs; a.o_bs = args->o_bs;
+    a.q_hs = args->q_hs; a.k_hs = args->k_hs; a.v_hs = args->v_hs; a.o_hs = args->o_hs;
+    a.ldq = args->ldq; a.ldk = args->ldk; a.ldv = args->ldv; a.ldo = args->ldo;
+    a.batch = args->batch; a.heads = args->heads; a.sq = args->sq; a.skv = args->skv; a.hd = args->hd;
+    a.scale = args->scale; a.causal = args->causal;
+    a.key_mask = args->key_mask; a.mask_ld = args->mask_ld;
+    a.rel_tab = args->rel_tab; a.rel_hs = args->rel_hs; a.rel_off = args->rel_off; a.rel_n = args->rel_n;
+    const int rc = launch_attention(a, (hipStream_t)stream);
+    if (form) *form = g_attn_form;
+    return rc;
+}
+#endif
