@@ -663,6 +663,30 @@ def load_rules() -> C.CDLL:
     return _load_companion(RULES_LIB_PATH, RULES_ABI_VERSION, declare)
 
 
+# ---- the flan-t5 beam-search companion library (include/eilev_t5beam.h): a fifth shared library with its own exports, loaded on demand.
+# It carries its own copy of the core library's code (linked from the same objects) and shares no state with it. ----
+T5BEAM_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_t5beam.so")
+T5BEAM_ABI_VERSION = 1
+T5BEAM_EXPORTS = ["eilev_t5beam_abi_version", "eilev_t5beam_cross_attention", "eilev_t5beam_decode_step", "eilev_t5beam_workspace_bytes"]
+
+
+def t5beam_supported(t5dims) -> bool:
+    """The models eilev_t5beam_decode_step takes (anything else returns EILEV_E_UNSUPPORTED): head size 64."""
+    return t5dims is not None and int(t5dims.d_kv) == 64
+
+
+def load_t5beam() -> C.CDLL:
+    """Load libeilev_hip_t5beam.so."""
+    def declare(sig):
+        TP = C.POINTER(T5Dims)
+        sig("eilev_t5beam_workspace_bytes", _sz, TP, _i64, _i64, _i64, _i64)
+        sig("eilev_t5beam_decode_step", _i32, TP, C.POINTER(T5Weights), vp, vp, vp, _i64, _i64, vp, vp, _i64, vp, vp, _i64, vp, vp, _sz, vp)
+        sig("eilev_t5beam_cross_attention", _i32, vp, _i64, vp, vp, vp, _i64, _i64, _i64, _i64, _i64, _i64, vp, vp, _sz, vp)
+        return sig("eilev_t5beam_abi_version", _i32)
+
+    return _load_companion(T5BEAM_LIB_PATH, T5BEAM_ABI_VERSION, declare)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         names = {-1: "EILEV_E_BADARG", -2: "EILEV_E_UNSUPPORTED", -3: "EILEV_E_WORKSPACE"}

@@ -507,7 +507,159 @@ __global__ __launch_bounds__(128) void attn_decode_merge_kernel(const float *__r
     if (t < hd) out[((int64_t)b * heads + h) * hd + t] = (bf16)(l > 0.0f ? o / l : 0.0f);
 }
 
+// ---- flan-t5 beam search: the cross-attention of the `beams` rows of one sample over THAT SAMPLE's encoder keys -------------------------------
+// The rows of a sample attend to the same K / V (eilev_t5_cross_kv writes them once per sample; nothing is replicated to the beams).  Grid
+// (heads, samples, 128-key ranges): thread (kg, c) requests 16-byte chunk c of keys kg, kg + 32, kg + 64, kg + 96 of the range, K and V,
+// straight to registers, ONCE, and keeps them while the sample's rows pass by in groups of 8: per group the scores of every row (the 8
+// chunk products of a key meet by shuffles among 8 neighbouring lanes), a softmax per row (waves 0 / 1 own rows 0..3 of the group, waves
+// 2 / 3 rows 4..7; thread = key), p . V with 8 x 8 accumulators, the key groups of a wave by shuffles, the four waves through LDS.  The
+// arithmetic of the other decode kernels: no scale, P rounded to bf16 for the product, the row sum from the unrounded P.  Leaves (max, sum,
+// o[64]) per (row, head, range) in the layout of attn_decode_part_bytes for attn_decode_merge_kernel.  Head size 64 only.
+// Slots at / beyond enc_len are never requested (the index is clamped into the range); a masked key's K may be anything (its score is
+// replaced before it is used) and its V is zeroed in registers, so 0 * NaN never reaches a sum.
+constexpr int XS_ROWS = 8, XS_KEYS = 128;
+__global__ __launch_bounds__(256) void attn_cross_shared_kernel(const bf16 *__restrict__ q, int64_t ldq, const bf16 *__restrict__ kc,
+                                                                const bf16 *__restrict__ vc, float *__restrict__ part,
+                                                                const int32_t *__restrict__ mask, int beams, int enc_len, int cap, int heads) {
+    constexpr int hd = 64, G = 32, VK = 4, NR = XS_ROWS, KEYS = XS_KEYS;
+    __shared__ __attribute__((aligned(16))) float qs[NR * hd];
+    __shared__ float sc[NR * KEYS];  // the scores of a group's rows, then their P rounded to bf16
+    __shared__ float wmax[NR * 2], wsum[NR * 2];
+    __shared__ float wacc[4 * NR * hd];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int h = blockIdx.x, smp = blockIdx.y, sp = blockIdx.z, nsplit = gridDim.z;
+    const int k0 = sp * KEYS, k1 = min(enc_len, k0 + KEYS);
+    auto rec = [&](int row) { return part + (((int64_t)row * heads + h) * nsplit + sp) * (hd + 2); };
+    if (k0 >= k1) {  // (the launcher sizes the grid by enc_len: not reached; a range with nothing in it)
+        if (tid < beams) {
+            float *po = rec(smp * beams + tid);
+            po[0] = -1e30f;
+            po[1] = 0.0f;
+        }
+        return;
+    }
+    const bf16 *kbase = kc + ((int64_t)smp * heads + h) * cap * hd, *vbase = vc + ((int64_t)smp * heads + h) * cap * hd;
+    const int32_t *mrow = mask ? mask + (int64_t)smp * enc_len : nullptr;
+    const int c = tid & 7, kg = tid >> 3;
+    bf16x8 kr[VK], vr[VK];
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        const int key = k0 + kg + i * G;
+        kr[i] = *reinterpret_cast<const bf16x8 *>(kbase + (int64_t)(key < k1 ? key : k1 - 1) * hd + c * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        const int key = k0 + kg + i * G;
+        vr[i] = *reinterpret_cast<const bf16x8 *>(vbase + (int64_t)(key < k1 ? key : k1 - 1) * hd + c * 8);
+    }
+    float kf[VK][8], vf[VK][8];
+#pragma unroll
+    for (int i = 0; i < VK; ++i) {
+        const int key = k0 + kg + i * G;
+        const bool vis = key < k1 && (!mrow || mrow[key < k1 ? key : k1 - 1] != 0);
+        unpack8(kr[i], kf[i]);
+        unpack8(vis ? vr[i] : zero8(), vf[i]);
+    }
+    const int key2 = tid & (KEYS - 1), half = tid >> 7;  // the softmax: thread = key, rows half * 4 .. half * 4 + 3 of the group
+    const bool vis2 = k0 + key2 < k1 && (!mrow || mrow[k0 + key2] != 0);
+    for (int r0 = 0; r0 < beams; r0 += NR) {
+        const int nr = min(NR, beams - r0);
+        for (int x = tid; x < nr * hd; x += 256) qs[x] = (float)q[(int64_t)(smp * beams + r0 + (x >> 6)) * ldq + h * hd + (x & 63)];
+        __syncthreads();  // (also: the group before has read sc, wmax, wsum and wacc)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            if (r < nr) {
+                const float4 q0 = *reinterpret_cast<const float4 *>(&qs[r * hd + c * 8]), q1 = *reinterpret_cast<const float4 *>(&qs[r * hd + c * 8 + 4]);
+#pragma unroll
+                for (int i = 0; i < VK; ++i) {
+                    const float *kv = kf[i];
+                    float dot = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
+                    dot += __shfl_xor(dot, 1, 64);
+                    dot += __shfl_xor(dot, 2, 64);
+                    dot += __shfl_xor(dot, 4, 64);
+                    if (c == 0) sc[r * KEYS + kg + i * G] = dot;
+                }
+            }
+        }
+        __syncthreads();
+        float s4[NR / 2];
+#pragma unroll
+        for (int rr = 0; rr < NR / 2; ++rr) {
+            const int r = half * (NR / 2) + rr;  // (uniform in a wave)
+            s4[rr] = -1e30f;
+            if (r < nr) {
+                s4[rr] = vis2 ? sc[r * KEYS + key2] : -1e30f;
+                const float m = wave_max(s4[rr]);
+                if (lane == 0) wmax[r * 2 + (wid & 1)] = m;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int rr = 0; rr < NR / 2; ++rr) {
+            const int r = half * (NR / 2) + rr;
+            if (r < nr) {
+                const float mx = fmaxf(wmax[r * 2], wmax[r * 2 + 1]);
+                const float p = s4[rr] > -1e29f ? __expf(s4[rr] - mx) : 0.0f;
+                sc[r * KEYS + key2] = (float)(bf16)p;  // P rounded to bf16 for the product; the row sum from the unrounded values
+                const float sw = wave_sum(p);
+                if (lane == 0) wsum[r * 2 + (wid & 1)] = sw;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            if (r < nr) {
+                float acc[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+#pragma unroll
+                for (int i = 0; i < VK; ++i) {
+                    const float pj = sc[r * KEYS + kg + i * G];  // (0 for a key at / beyond k1 and for a masked one)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[e] += pj * vf[i][e];
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {  // the 8 key groups of a wave hold chunk c in lanes c, c + 8, ...
+                    float v = acc[e];
+                    v += __shfl_xor(v, 8, 64);
+                    v += __shfl_xor(v, 16, 64);
+                    v += __shfl_xor(v, 32, 64);
+                    if (lane < 8) wacc[(wid * NR + r) * hd + c * 8 + e] = v;
+                }
+            }
+        }
+        __syncthreads();
+        for (int x = tid; x < nr * hd; x += 256) {
+            const int r = x >> 6, dd = x & 63;
+            rec(smp * beams + r0 + r)[2 + dd] = (wacc[r * hd + dd] + wacc[(NR + r) * hd + dd]) + (wacc[(2 * NR + r) * hd + dd] + wacc[(3 * NR + r) * hd + dd]);
+        }
+        if (tid < nr) {
+            float *po = rec(smp * beams + r0 + tid);
+            po[0] = fmaxf(wmax[tid * 2], wmax[tid * 2 + 1]);
+            po[1] = wsum[tid * 2] + wsum[tid * 2 + 1];
+        }
+    }
+}
+
 }  // namespace
+
+// The rows of a sample share its K / V (flan-t5 beam search): attn_cross_shared_kernel over 128-key ranges, then the merge.  q: `rows` query
+// rows of stride ldq; kc / vc: planes [rows / beams][heads][cap][64], keys [0, enc_len); enc_mask (rows / beams, enc_len) or null.
+int launch_attn_cross_shared(const bf16 *q, int64_t ldq, const bf16 *kc, const bf16 *vc, const int32_t *enc_mask, int rows, int beams, int heads,
+                             int hd, int enc_len, int cap, bf16 *out, float *part, size_t part_bytes, hipStream_t s) {
+    if (!q || !kc || !vc || !out || !part) return EILEV_E_BADARG;
+    if (rows <= 0 || beams <= 0 || rows % beams || rows > 32 || beams > 32 || heads <= 0 || enc_len <= 0 || cap < enc_len || ldq < (int64_t)heads * hd)
+        return EILEV_E_BADARG;
+    if ((((uintptr_t)kc | (uintptr_t)vc) & 15) != 0) return EILEV_E_BADARG;  // (16-byte loads)
+    if (hd != 64) return EILEV_E_UNSUPPORTED;
+    if (part_bytes < attn_decode_part_bytes(rows, heads, hd, enc_len, XS_KEYS)) return EILEV_E_WORKSPACE;
+    const int ns = (int)ceil_div64(enc_len, XS_KEYS);
+    hipLaunchKernelGGL(attn_cross_shared_kernel, dim3(heads, rows / beams, ns), dim3(256), 0, s, q, ldq, kc, vc, part, enc_mask, beams, enc_len, cap, heads);
+    EILEV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(heads, rows), dim3(128), 0, s, part, out, heads, hd, ns);
+    EILEV_LAUNCH_CHECK();
+    return EILEV_OK;
+}
 
 static int g_beam_part = 1;
 static int g_attn_part32 = 1;  // 1 = by batch size (launch_attn_decode); probe build: 0 = the 256-key split kernel, 2 / 3 = force a form

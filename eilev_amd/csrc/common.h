@@ -511,6 +511,12 @@ bool attn_decode1_ok(int batch, int cap, int hd);
 int launch_attn_decode1(const DecodeAttnArgs &a, hipStream_t s);
 // ... the same loading scheme over 128-key ranges, partials for gemv1_kernel's merge prologue; *nsplit = the ranges per (row, head)
 int launch_attn_decode_part(const DecodeAttnArgs &a, hipStream_t s, int *nsplit);
+// flan-t5 beam search: the cross-attention of `rows` query rows (stride ldq, head size 64) of which every `beams` consecutive ones share one
+// sample's keys / values — planes [rows / beams][heads][cap][hd], keys [0, enc_len), enc_mask (rows / beams, enc_len) or null — read once
+// per (sample, head, 128-key range); partials in `part` (attn_decode_part_bytes(rows, heads, hd, enc_len)), merged into out [rows][heads * hd].
+// No scale, no bias.  hd != 64: EILEV_E_UNSUPPORTED before any launch.
+int launch_attn_cross_shared(const bf16 *q, int64_t ldq, const bf16 *kc, const bf16 *vc, const int32_t *enc_mask, int rows, int beams, int heads,
+                             int hd, int enc_len, int cap, bf16 *out, float *part, size_t part_bytes, hipStream_t s);
 int launch_rmsnorm(const bf16 *x, int64_t ldx, const bf16 *g, bf16 *y, int64_t ldy, int64_t rows, int cols, float eps, hipStream_t s);
 
 void prof_begin(int kind, double flops, hipStream_t s);

@@ -95,5 +95,21 @@ static inline bool dims_ok_t5(const EilevT5Dims *d) {
            d->rel_buckets >= 4 && d->rel_max_dist > d->rel_buckets / 4;
 }
 
+// t5.hip: the beam form of the flan-t5 decode step (include/eilev_t5beam.h holds the layout; t5beam.hip is its C ABI).  Row r is beam
+// r % beams of sample r / beams; the decoder start token's K / V sit in kv_start (one row per sample, capacity 1: eilev_t5_decode fills
+// it), generated token g of a hypothesis in slot g of kv_gen (one row per beam slot, capacity gen_capacity), in row ancestors[g][r].
+struct T5BeamArgs {
+    int64_t beams;
+    const void *kv_start;
+    void *kv_gen;
+    int64_t gen_capacity;
+    const int32_t *ancestors;
+};
+// One step on `rows` rows: state[0] = generated tokens fed including this one (the decoder position of the query); incremented at the end.
+int t5_decode_step_beam(const EilevT5Dims *d, const EilevT5Weights *w, const int64_t *tokens, int32_t *state, const int32_t *enc_mask,
+                        int64_t rows, const T5BeamArgs &beam, const void *cross_kv, int64_t enc_len, float *logits, void *workspace,
+                        size_t workspace_bytes, void *stream);
+size_t t5_decode_step_beam_workspace_bytes(const EilevT5Dims *d, int64_t rows, int64_t enc_len, int64_t gen_capacity);
+
 // probe / test switches read outside the unit that defines them (set by eilev_debug_* of the probe build)
 extern int g_decode_rows;  // opt.hip; eilev_linear_rows (blocks.hip) follows it

@@ -133,15 +133,22 @@ extern "C" int eilev_t5_cross_kv(const EilevT5Dims *d, const EilevT5Weights *w, 
 
 // `state` != null: single-token step whose position is state[0] on the device (host past_len = 0, the buffers are sized
 // for the whole capacity); null: positions past_len .. past_len + new_len - 1 given by the host
+// `beam` != null (with `state`; stages.h T5BeamArgs): the step of beam search that moves no cache row.  self_kv is then the START cache (one
+// row per sample, capacity 1) and kv_capacity = 1 + gen_capacity; the self-attention takes the ancestor form of the split kernel (key 0 =
+// the start token, key 1 + g = generation slot g of row ancestors[g][r], the new token to the row's own slot state[0] - 1), the
+// cross-attention the kernel in which a sample's rows share its K / V (cross_kv and enc_mask have one row per SAMPLE)
 static int t5_decode_impl(const EilevT5Dims *d, const EilevT5Weights *w, const int64_t *dec_ids, const int32_t *enc_mask,
                           int64_t batch, int64_t new_len, int64_t past_len, const int32_t *state, void *self_kv, int64_t kv_capacity,
                           const void *cross_kv, int64_t enc_len, float *logits, void *workspace, size_t workspace_bytes,
-                          void *stream, const int32_t *dec_mask = nullptr, void *hidden_out = nullptr) {
+                          void *stream, const int32_t *dec_mask = nullptr, void *hidden_out = nullptr, const T5BeamArgs *beam = nullptr) {
     if (!d || !w || !dec_ids || !enc_mask || !self_kv || !cross_kv || !logits || !workspace) return EILEV_E_BADARG;
     if (state && (dec_mask || hidden_out)) return EILEV_E_BADARG;
     if (batch <= 0 || new_len <= 0 || past_len < 0 || past_len + new_len > kv_capacity || enc_len <= 0) return EILEV_E_BADARG;
     if (state && (new_len != 1 || past_len != 0)) return EILEV_E_BADARG;
-    if (!dims_ok_t5(d)) return EILEV_E_UNSUPPORTED;
+    if (beam && (!state || !beam->kv_gen || !beam->ancestors || beam->beams <= 0 || beam->beams > 32 || batch > 32 || batch % beam->beams ||
+                 beam->gen_capacity <= 0 || kv_capacity != beam->gen_capacity + 1))
+        return EILEV_E_BADARG;
+    if (!dims_ok_t5(d) || (beam && d->d_kv != 64)) return EILEV_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const int D = d->d_model, H = d->heads, hd = d->d_kv, I = H * hd;
     const int64_t M = batch * new_len, total = state ? kv_capacity : past_len + new_len;  // with `state`: an upper bound
@@ -152,16 +159,19 @@ static int t5_decode_impl(const EilevT5Dims *d, const EilevT5Weights *w, const i
     // (with `state` the table holds the single query row at position state[0]: entry j = bias of key j)
     RC(launch_t5_rel_table((const bf16 *)w->dec_rel_bias, b.rel, (int)total, (int)total - 1, H, 0, d->rel_buckets, d->rel_max_dist, s,
                            state));
-    const KvCache skv(batch, I, kv_capacity), ckv(batch, I, enc_len);
+    const int64_t samples = beam ? batch / beam->beams : batch;
+    const KvCache skv(samples, I, beam ? 1 : kv_capacity), ckv(samples, I, enc_len), gkv(batch, I, beam ? beam->gen_capacity : 0);
     // single-query steps: the decode-attention kernels (the self-attention over keys 0 .. total - 1 of the cache, the bias of one query row)
     DecodeAttnArgs sa = decode_attn_args(b.qkv, b.att, b.scratch, batch, H, hd), ca = sa;
     sa.ldq = 3 * (int64_t)I; sa.attn_mask = dec_mask; sa.cap = (int)kv_capacity; sa.rel_tab = b.rel; sa.rel_hs = total;
     // with `state`: kv_total = 1 + state[0] on the device, the table is this query's row (entry j = key j), the kernel stores the new K / V
     sa.state = state; sa.seq_len = state ? 1 : (int)total; sa.rel_off = state ? -1 : (int)total - 1; sa.fuse_new = state ? 1 : 0;
     ca.ldq = I; ca.attn_mask = enc_mask; ca.seq_len = ca.cap = (int)enc_len;
+    if (beam) { sa.cap = 1; sa.anc = beam->ancestors; sa.beams = (int)beam->beams; sa.cap_g = (int)beam->gen_capacity; }
     const int64_t kmax = kv_capacity > enc_len ? kv_capacity : enc_len;
     const bool single = new_len == 1 && attn_decode_part_bytes((int)batch, H, hd, (int)kmax) <= sa.part_bytes;
     if (state && !single) return EILEV_E_UNSUPPORTED;
+    if (beam && attn_decode_part_bytes((int)batch, H, hd, (int)kv_capacity, 256) > sa.part_bytes) return EILEV_E_UNSUPPORTED;
     const size_t hid_bytes = (size_t)M * D * sizeof(bf16);
     const bool fuse_norm = single && M <= 32 && !hidden_out;  // the weight-streaming GEMVs of a decode step (their reduce can carry a norm)
     for (int l = 0; l < d->dec_layers; ++l) {
@@ -181,6 +191,7 @@ static int t5_decode_impl(const EilevT5Dims *d, const EilevT5Weights *w, const i
         }
         if (single) {
             sa.kc = kc; sa.vc = vc;
+            if (beam) { sa.kg = gkv.k((bf16 *)beam->kv_gen, l); sa.vg = gkv.v((bf16 *)beam->kv_gen, l); }
             RC(launch_attn_decode(sa, s));
         } else {
             AttnArgs a = attn_cache(b.qkv, 3 * I, kc, vc, kv_capacity, b.att, batch, H, new_len, total, hd, 1.0f);
@@ -197,7 +208,10 @@ static int t5_decode_impl(const EilevT5Dims *d, const EilevT5Weights *w, const i
         // ---- cross-attention over the encoder output (T5LayerCrossAttention :404-432): no position bias, padding mask
         if (!fuse_norm) RC(launch_rmsnorm(b.h, D, (const bf16 *)L->ln_ca, b.x, D, M, D, d->eps, s));
         RC(launch_gemm(t5_gemm(b, b.x, D, L->cq_w, D, nullptr, 0, b.qkv, I, M, I, D), 5, s));
-        if (single) {
+        if (beam) {
+            RC(launch_attn_cross_shared(b.qkv, I, ck, cv, enc_mask, (int)batch, (int)beam->beams, H, hd, (int)enc_len, (int)enc_len, b.att, ca.part,
+                                        ca.part_bytes, s));
+        } else if (single) {
             ca.kc = ck; ca.vc = cv;
             RC(launch_attn_decode(ca, s));
         } else {
@@ -245,4 +259,24 @@ extern "C" int eilev_t5_decode_step(const EilevT5Dims *d, const EilevT5Weights *
     if (!state) return EILEV_E_BADARG;
     return t5_decode_impl(d, w, tokens, enc_mask, batch, 1, 0, state, self_kv, kv_capacity, cross_kv, enc_len, logits, workspace,
                           workspace_bytes, stream);
+}
+
+// ---- the beam form as a plain C++ function for t5beam.hip (stages.h): not an entry of include/eilev.h -------------------------------------
+namespace {
+__global__ void t5_bump_step_kernel(int32_t *state) {
+    if (threadIdx.x == 0) state[0] += 1;
+}
+}  // namespace
+size_t t5_decode_step_beam_workspace_bytes(const EilevT5Dims *d, int64_t rows, int64_t enc_len, int64_t gen_capacity) {
+    return eilev_t5_workspace_bytes(d, rows, 1, enc_len > gen_capacity + 1 ? enc_len : gen_capacity + 1);
+}
+int t5_decode_step_beam(const EilevT5Dims *d, const EilevT5Weights *w, const int64_t *tokens, int32_t *state, const int32_t *enc_mask,
+                        int64_t rows, const T5BeamArgs &beam, const void *cross_kv, int64_t enc_len, float *logits, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+    if (!state || !beam.kv_start) return EILEV_E_BADARG;
+    RC(t5_decode_impl(d, w, tokens, enc_mask, rows, 1, 0, state, const_cast<void *>(beam.kv_start), beam.gen_capacity + 1, cross_kv, enc_len, logits,
+                      workspace, workspace_bytes, stream, nullptr, nullptr, &beam));
+    t5_bump_step_kernel<<<1, 64, 0, (hipStream_t)stream>>>(state);  // the step counter lives on the device: a captured step replays for every step
+    EILEV_LAUNCH_CHECK();
+    return EILEV_OK;
 }

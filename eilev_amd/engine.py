@@ -744,10 +744,8 @@ class HipEngine:
         # The fused form of the device loop, stated once as the two facts used below: the per-row top-k kernel takes this call (its vocabulary,
         # `keep` candidates per row), and so does the kernel that advances the hypotheses
         eos_l = eos_list(eos_id)
-        keep = max(2, 1 + len(eos_l)) * num_beams
         gen_cap = max(1, max_new_tokens)
-        topk_ok = self.beam_topk_kernel and d.vocab <= 65536 and d.vocab % 4 == 0 and keep <= 64
-        advance_ok = topk_ok and self.beam_advance_kernel and num_beams * keep <= 2048 and gen_cap * num_beams <= 2048 and len(eos_l) <= 8
+        topk_ok, advance_ok = self._beam_kernels_ok(d.vocab, num_beams, eos_l, gen_cap)
         device_loop = sampler is None and num_beams > 1 and self.beam_device_loop
         rules_kw, with_rules, rules_in = None, False, rules
         if sampler is not None and num_beams == 1 and not sampler.get("greedy"):
@@ -819,65 +817,9 @@ class HipEngine:
         if device_loop and (rules_kw is not None or (not rules and int(min_new_tokens) == 0)) and trace is None:
             # (r4) plain beam search — the sample script's call: selection, ancestor-table update and the decode step as ONE captured graph per
             # generated token, nothing indexed by the step on the host (eilev_amd/beam.py::beam_search_device)
-            from .beam import beam_search_device
-
-            tpos = torch.zeros(1, dtype=torch.int64, device=self.device)
-            ident_row = ident32.view(1, R)
-            state[0] = 1
-
-            def step_dev(next_tokens, beam_src):
-                anc.copy_(anc.index_select(1, beam_src))  # rows of steps not reached yet hold stale slots: row t is set before it is ever read
-                anc.index_copy_(0, tpos, ident_row)
-                tokens.copy_(next_tokens)
-                launch()
-                tpos.add_(1)
-
-            topk_fn = None
-            if topk_ok:
-                row_lp = torch.empty((R, keep), dtype=torch.float32, device=self.device)
-                row_tok = torch.empty((R, keep), dtype=torch.int32, device=self.device)
-
-                def topk_fn(buf, run_score):
-                    abi.check(self.lib.eilev_topk_logprob(_ptr(buf), _ptr(run_score), R, d.vocab, keep, _ptr(row_lp), _ptr(row_tok), self._stream()),
-                              "eilev_topk_logprob")
-                    return row_lp, row_tok
-
-            advance_fn = None
-            if advance_ok:
-                eos_arr = (C.c_int64 * max(1, len(eos_l)))(*eos_l)
-                scratch = torch.empty(int(self.lib.eilev_beam_scratch_bytes(B, num_beams, keep, max_new_tokens)), dtype=torch.uint8, device=self.device)
-
-                def advance_fn(lp_rows, tok_rows, st):  # the whole bookkeeping of a step, the tokens to feed and the ancestor table: one kernel
-                    abi.check(self.lib.eilev_beam_advance(
-                        _ptr(lp_rows), _ptr(tok_rows), B, num_beams, keep, max_new_tokens, _ptr(state), eos_arr, len(eos_l), _ptr(st["pow_tab"]),
-                        int(st["reciprocal"]), int(st["early"]), _ptr(st["run_seq"]), _ptr(st["run_score"]), _ptr(st["fin_seq"]), _ptr(st["fin_score"]),
-                        _ptr(st["fin_len"]), _ptr(st["finished"]), _ptr(st["can_improve"]), _ptr(tokens), _ptr(anc), gen_cap, _ptr(scratch),
-                        scratch.numel(), self._stream()), "eilev_beam_advance")
-
-                def step_dev(next_tokens, beam_src):  # noqa: F811 (tokens / ancestors were written by eilev_beam_advance)
-                    launch()
-
-            # with the two selection kernels a step is ONE C call that enqueues ~260 kernels (2.5 ms of GPU work): capturing it buys nothing per
-            # token (2.565 vs 2.554 ms) and costs ~1.2 ms per generate() call — replayed graphs only on request (`engine.beam_capture = True`)
-            # or when the selection runs as torch ops
-            capture = use_graph and (advance_fn is None or self.beam_capture)
-            if rules_kw is not None:
-                # the rules of the call inside the per-row selection (eilev_rules_topk_logprob): row r's history is run_seq[r, 0 .. cur), which
-                # eilev_beam_advance keeps in place, and cur = state[0] - 1 is the decode step's device counter (allow_device: advance_ok holds)
-                rl = abi.load_rules()
-                p_rules = abi.rules_params(rules_kw["repetition_penalty"], rules_kw["no_repeat_ngram_size"], rules_kw["min_new_tokens"], max_new_tokens,
-                                           eos_l, pad_id, -1, 0, 0)
-
-                def topk_fn(buf, run_score, run_seq, cur_t):  # noqa: F811
-                    abi.check(rl.eilev_rules_topk_logprob(C.byref(p_rules), _ptr(buf), _ptr(run_score), R, d.vocab, keep, _ptr(state), _ptr(run_seq),
-                                                          _ptr(row_lp), _ptr(row_tok), None, None, 0, self._stream()), "eilev_rules_topk_logprob")
-                    return row_lp, row_tok
-
-            out = beam_search_device(step_dev, logits, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
-                                     num_return_sequences, use_graph=capture, topk_fn=topk_fn, advance_fn=advance_fn, topk_history=rules_kw is not None)
+            out = self._beam_device_loop(launch, last, B, num_beams, max_new_tokens, d.vocab, state, tokens, anc, logits, length_penalty, eos_id, pad_id,
+                                         early_stopping, num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok)
             self._decode_warm = True
-            if rules_kw is not None:
-                self.rules_stats = dict(path="device", steps=int(out.shape[1]))
             return out
         if sampler is not None and num_beams == 1:  # multinomial sampling: eilev_amd/sampling.py on the same decode step
             from .sampling import sample_loop
@@ -888,6 +830,84 @@ class HipEngine:
                               num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
         self._host_stats(ids, sampler, num_beams, with_rules)
         return ids
+
+    def _beam_kernels_ok(self, vocab, num_beams, eos_l, gen_cap):
+        """(topk_ok, advance_ok) of a beam search call: the per-row top-k kernel takes it (its vocabulary, `keep` candidates per row), and so
+        does the kernel that advances the hypotheses."""
+        keep = max(2, 1 + len(eos_l)) * num_beams
+        topk_ok = self.beam_topk_kernel and vocab <= 65536 and vocab % 4 == 0 and keep <= 64
+        advance_ok = topk_ok and self.beam_advance_kernel and num_beams * keep <= 2048 and gen_cap * num_beams <= 2048 and len(eos_l) <= 8
+        return topk_ok, advance_ok
+
+    def _beam_device_loop(self, launch, first, B, num_beams, max_new_tokens, vocab, state, tokens, anc, logits, length_penalty, eos_id, pad_id,
+                          early_stopping, num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok, prefix_id=-1):
+        """beam_search_device around ``launch()``, a decode step in the beam form (eilev_opt_decode_step_beam, eilev_t5beam_decode_step) that
+        feeds ``tokens`` (R,), reads the ancestor table ``anc`` (gen_cap, R) and the counter ``state``, leaves the logits in ``logits`` (R, vocab)
+        and increments state[0].  ``first``: the (B, vocab) logits in front of the first selection.  ``prefix_id``: the id the rules see in front
+        of a hypothesis (flan-t5's decoder start token)."""
+        from .beam import beam_search_device
+        from .sampling import eos_list
+
+        eos_l = eos_list(eos_id)
+        keep = max(2, 1 + len(eos_l)) * num_beams
+        gen_cap, R = anc.shape
+        tpos = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ident_row = torch.arange(R, dtype=torch.int32, device=self.device).view(1, R)
+        state[0] = 1
+
+        def step_dev(next_tokens, beam_src):
+            anc.copy_(anc.index_select(1, beam_src))  # rows of steps not reached yet hold stale slots: row t is set before it is ever read
+            anc.index_copy_(0, tpos, ident_row)
+            tokens.copy_(next_tokens)
+            launch()
+            tpos.add_(1)
+
+        topk_fn = None
+        if topk_ok:
+            row_lp = torch.empty((R, keep), dtype=torch.float32, device=self.device)
+            row_tok = torch.empty((R, keep), dtype=torch.int32, device=self.device)
+
+            def topk_fn(buf, run_score):
+                abi.check(self.lib.eilev_topk_logprob(_ptr(buf), _ptr(run_score), R, vocab, keep, _ptr(row_lp), _ptr(row_tok), self._stream()),
+                          "eilev_topk_logprob")
+                return row_lp, row_tok
+
+        advance_fn = None
+        if advance_ok:
+            eos_arr = (C.c_int64 * max(1, len(eos_l)))(*eos_l)
+            scratch = torch.empty(int(self.lib.eilev_beam_scratch_bytes(B, num_beams, keep, max_new_tokens)), dtype=torch.uint8, device=self.device)
+
+            def advance_fn(lp_rows, tok_rows, st):  # the whole bookkeeping of a step, the tokens to feed and the ancestor table: one kernel
+                abi.check(self.lib.eilev_beam_advance(
+                    _ptr(lp_rows), _ptr(tok_rows), B, num_beams, keep, max_new_tokens, _ptr(state), eos_arr, len(eos_l), _ptr(st["pow_tab"]),
+                    int(st["reciprocal"]), int(st["early"]), _ptr(st["run_seq"]), _ptr(st["run_score"]), _ptr(st["fin_seq"]), _ptr(st["fin_score"]),
+                    _ptr(st["fin_len"]), _ptr(st["finished"]), _ptr(st["can_improve"]), _ptr(tokens), _ptr(anc), gen_cap, _ptr(scratch),
+                    scratch.numel(), self._stream()), "eilev_beam_advance")
+
+            def step_dev(next_tokens, beam_src):  # noqa: F811 (tokens / ancestors were written by eilev_beam_advance)
+                launch()
+
+        # with the two selection kernels a step is ONE C call that enqueues ~260 kernels (2.5 ms of GPU work): capturing it buys nothing per
+        # token (2.565 vs 2.554 ms) and costs ~1.2 ms per generate() call — replayed graphs only on request (`engine.beam_capture = True`)
+        # or when the selection runs as torch ops
+        capture = use_graph and (advance_fn is None or self.beam_capture)
+        if rules_kw is not None:
+            # the rules of the call inside the per-row selection (eilev_rules_topk_logprob): row r's history is run_seq[r, 0 .. cur), which
+            # eilev_beam_advance keeps in place, and cur = state[0] - 1 is the decode step's device counter (allow_device: advance_ok holds)
+            rl = abi.load_rules()
+            p_rules = abi.rules_params(rules_kw["repetition_penalty"], rules_kw["no_repeat_ngram_size"], rules_kw["min_new_tokens"], max_new_tokens,
+                                       eos_l, pad_id, prefix_id, 0, 0)
+
+            def topk_fn(buf, run_score, run_seq, cur_t):  # noqa: F811
+                abi.check(rl.eilev_rules_topk_logprob(C.byref(p_rules), _ptr(buf), _ptr(run_score), R, vocab, keep, _ptr(state), _ptr(run_seq),
+                                                      _ptr(row_lp), _ptr(row_tok), None, None, 0, self._stream()), "eilev_rules_topk_logprob")
+                return row_lp, row_tok
+
+        out = beam_search_device(step_dev, logits, first, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
+                                 num_return_sequences, use_graph=capture, topk_fn=topk_fn, advance_fn=advance_fn, topk_history=rules_kw is not None)
+        if rules_kw is not None:
+            self.rules_stats = dict(path="device", steps=int(out.shape[1]))
+        return out
 
     def _host_stats(self, ids, sampler, num_beams, with_rules):
         """What a call that ran one of the host loops (sample_loop, beam_search) records: sample_stats when it drew, rules_stats when it
@@ -1486,29 +1506,43 @@ class HipEngine:
         return torch.cat((start, out[:c].reshape(1, c)), dim=1)
 
     def t5_beam(self, inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty=1.0, eos_id=1, pad_id=0, start_id=0,
-                early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, rules=None):
-        """Beam search for the encoder-decoder LM [sample default num_beams=5, length_penalty=-1; hf generation/utils.py:3208+]:
-        the encoder runs once per sample, its cross K/V are replicated to the beams, every step reorders the self-attention
-        cache rows by the surviving beams' parents and runs one decoder step on all rows."""
+                early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, rules=None, use_graph=True):
+        """Beam search for the encoder-decoder LM [sample default num_beams=5, length_penalty=-1; hf generation/utils.py:3208+].
+
+        The device loop (plain beam search and the numeric rules, head size 64, at most 32 beams; `_t5_beam_device`): the encoder and the cross
+        K/V once per SAMPLE, no cache row ever copied or replicated, selection + ancestor table + decode step per token as in beam_decode.
+        Everything else (beam-search sampling, user processors, stopping criteria, num_beams == 1, other head sizes, ``beam_device_loop =
+        False``) keeps the host loop: the cross K/V replicated to the beams, every step reorders the self-attention cache rows by the
+        surviving beams' parents and runs eilev_t5_decode on all rows.  ``self.t5_beam_stats`` = dict(path="device" | "host", steps=n)."""
         from .beam import beam_search
+        from .sampling import eos_list
 
         # hf generation/utils.py:3319 `output_fill_value = pad_token_id or eos_token_id[0] ...`: a pad id of 0 (T5) is falsy,
         # so finished hypotheses are padded with the EOS id
         if pad_id == 0 and num_beams > 1:
-            from .sampling import eos_list
-
             e = eos_list(eos_id)
             pad_id = e[0] if e else -1
         d = self.t5dims
-        with_rules = False
+        with_rules, rules_kw, rules_in = False, None, rules
+        eos_l = eos_list(eos_id)
+        topk_ok, advance_ok = self._beam_kernels_ok(d.vocab, num_beams, eos_l, max(1, max_new_tokens))
+        device_loop = sampler is None and 1 < num_beams <= 32 and max_new_tokens > 0 and self.beam_device_loop and abi.t5beam_supported(d)
         if sampler is None or sampler.get("greedy") or num_beams > 1:
-            # greedy search with rules runs on the device (t5_rules_device); beam search has no device loop for this model: its rules, numbers
-            # included, run in the host loop
+            # greedy search with rules runs on the device (t5_rules_device), and so does beam search when it takes the fused form of the device
+            # loop; else the rules, numbers included, run in the host loop
             greedy1 = sampler is not None and num_beams == 1
             min_new = int(sampler.get("min_new_tokens", 0) or 0) if sampler is not None else int(min_new_tokens)
-            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, allow_device=greedy1)
-            if rules_kw is not None:
+            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, allow_device=greedy1 or (device_loop and advance_ok))
+            if rules_kw is not None and greedy1:
                 return self.t5_rules_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, start_id=start_id, **rules_kw)
+        if device_loop and (rules_kw is not None or (not rules and int(min_new_tokens) == 0)):
+            per = max(1, 32 // num_beams)
+            if inputs_embeds.shape[0] > per:  # at most 32 decode rows per call: sample group by sample group (every part is routed again)
+                return self._chunked_rows(lambda i, j: self.t5_beam(
+                    inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, num_beams, length_penalty, eos_id, pad_id, start_id, early_stopping,
+                    num_return_sequences, None, min_new_tokens, rules_in, use_graph), inputs_embeds.shape[0], pad_id, "t5_beam_stats", per=per)
+            return self._t5_beam_device(inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty, eos_id, pad_id, start_id,
+                                        early_stopping, num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok)
         if sampler is not None and num_beams == 1:
             dev_kw = None
             if not sampler.get("greedy"):
@@ -1544,6 +1578,43 @@ class HipEngine:
             ids = beam_search(step, first[::num_beams].contiguous(), B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id,
                               early_stopping, num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
         self._host_stats(ids, sampler, num_beams, with_rules)
+        self.t5_beam_stats = dict(path="host", steps=int(ids.shape[1]))
+        head = torch.full((ids.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
+        return torch.cat((head, ids), dim=1)
+
+    def _t5_beam_device(self, inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty, eos_id, pad_id, start_id, early_stopping,
+                        num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok):
+        """The device loop of t5_beam on B * num_beams <= 32 rows (include/eilev_t5beam.h holds the layout).  The decoder start token plays the
+        part of OPT's prompt: eilev_t5_decode on the B samples fills a start cache of capacity 1 and gives the first logits; generated
+        tokens go to a generation cache with one row per beam slot, found through the ancestor table that eilev_beam_advance keeps; the
+        cross K/V and the padding mask stay one row per sample.  `_beam_device_loop` with eilev_t5beam_decode_step as the step; the rules
+        see the start token in front of a hypothesis (prefix_id), as hf's processors do."""
+        d = self.t5dims
+        tb = abi.load_t5beam()
+        enc = self.t5_encode(inputs_embeds, attention_mask)
+        B, L, _ = enc.shape
+        R = B * num_beams
+        gen_cap = max(1, max_new_tokens)
+        ckv = self.t5_cross_kv(enc)
+        am = attention_mask.to(self.device, torch.int32).contiguous()
+        kv_start = torch.empty(int(self.lib.eilev_t5_self_kv_bytes(C.byref(d), B, 1)), dtype=torch.uint8, device=self.device)
+        start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
+        first = self.t5_decode(start, am, 0, kv_start, 1, ckv, L)[:, 0].contiguous()
+        kv_gen = torch.empty(int(self.lib.eilev_t5_self_kv_bytes(C.byref(d), R, gen_cap)), dtype=torch.uint8, device=self.device)
+        anc = torch.zeros((gen_cap, R), dtype=torch.int32, device=self.device)
+        state = torch.zeros(2, dtype=torch.int32, device=self.device)
+        tokens = torch.zeros(R, dtype=torch.int64, device=self.device)
+        logits = torch.empty((R, d.vocab), dtype=torch.float32, device=self.device)
+        ws = self._workspace("t5beam", int(tb.eilev_t5beam_workspace_bytes(C.byref(d), R, num_beams, L, gen_cap)))
+
+        def launch():
+            abi.check(tb.eilev_t5beam_decode_step(
+                C.byref(d), C.byref(self.pack.t5), _ptr(tokens), _ptr(state), _ptr(am), R, num_beams, _ptr(kv_start), _ptr(kv_gen), gen_cap, _ptr(anc),
+                _ptr(ckv), L, _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_t5beam_decode_step")
+
+        ids = self._beam_device_loop(launch, first, B, num_beams, max_new_tokens, d.vocab, state, tokens, anc, logits, length_penalty, eos_id, pad_id,
+                                     early_stopping, num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok, prefix_id=int(start_id))
+        self.t5_beam_stats = dict(path="device", steps=int(ids.shape[1]))
         head = torch.full((ids.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
         return torch.cat((head, ids), dim=1)
 

@@ -9,8 +9,9 @@ state-dict names; none of them has arithmetic in its ``forward``
 ``forward`` or ``generate`` on a model that is not on an AMD GPU raises.
 
 Not built (raise ``NotImplementedError``): contrastive / group-beam decoding (greedy, multinomial sampling, beam search and beam-search sampling
-are).  ``generate`` takes ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_new_tokens`` and several EOS ids as numbers: greedy search, sampling and (OPT)
-beam search apply them on the device in the captured decode step; user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
+are).  ``generate`` takes ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_new_tokens`` and several EOS ids as numbers: greedy search, sampling and
+beam search apply them on the device in the decode step, for OPT and for flan-t5 (whose beam search runs on the device at head size 64, without
+copying or replicating a cache: include/eilev_t5beam.h); beam-search sampling and user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
 ``output_hidden_states`` / ``output_attentions`` inside the full model's ``forward`` are served from slow paths for the vision wrapper,
 the Q-Former (self- and cross-attention weights), the OPT language model and the T5 stacks (hidden states; self- and cross-attention weights).  ``decoder_attention_mask`` with padding is honoured on the evaluation route (the first target position of a row must stay visible).
 """
