@@ -687,6 +687,33 @@ def load_t5beam() -> C.CDLL:
     return _load_companion(T5BEAM_LIB_PATH, T5BEAM_ABI_VERSION, declare)
 
 
+# ---- the shared-prefix companion library (include/eilev_prefix.h): rows of new positions that continue one cached prefix, stored once.
+# Like the flan-t5 beam library it carries its own copy of the core library's code and shares no state with it. ----
+PREFIX_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_prefix.so")
+PREFIX_ABI_VERSION = 1
+PREFIX_MAX_ROWS = 4096
+PREFIX_MAX_NEW = 2048
+PREFIX_MAX_STACKED = 65536
+PREFIX_EXPORTS = ["eilev_prefix_abi_version", "eilev_prefix_attention", "eilev_prefix_extend", "eilev_prefix_workspace_bytes"]
+
+
+def prefix_supported(dims) -> bool:
+    """The models eilev_prefix_extend takes (anything else returns EILEV_E_UNSUPPORTED): head sizes 80 and 128."""
+    return dims is not None and int(dims.t_heads) > 0 and int(dims.t_hidden) // int(dims.t_heads) in (80, 128)
+
+
+def load_prefix() -> C.CDLL:
+    """Load libeilev_hip_prefix.so."""
+    def declare(sig):
+        DP = C.POINTER(Dims)
+        sig("eilev_prefix_attention", _i32, vp, _i64, vp, _i64, vp, _i64, vp, vp, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, vp, vp)
+        sig("eilev_prefix_workspace_bytes", _sz, DP, _i64, _i64)
+        sig("eilev_prefix_extend", _i32, DP, C.POINTER(OptWeights), vp, _i64, _i64, vp, _i64, vp, _i64, vp, vp, vp, _sz, vp)
+        return sig("eilev_prefix_abi_version", _i32)
+
+    return _load_companion(PREFIX_LIB_PATH, PREFIX_ABI_VERSION, declare)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         names = {-1: "EILEV_E_BADARG", -2: "EILEV_E_UNSUPPORTED", -3: "EILEV_E_WORKSPACE"}

@@ -1,6 +1,7 @@
 """Builds eilev_amd/csrc/libeilev_hip.so and its companions libeilev_hip_pld.so (prompt lookup), libeilev_hip_sample.so (device
-sampling), libeilev_hip_rules.so (logits rules of greedy and beam search) and libeilev_hip_t5beam.so (the flan-t5 decode step of beam search:
-its own unit t5beam.o linked with the core library's objects, include/eilev_t5beam.h) (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
+sampling), libeilev_hip_rules.so (logits rules of greedy and beam search), libeilev_hip_t5beam.so (the flan-t5 decode step of beam search:
+its own unit t5beam.o linked with the core library's objects, include/eilev_t5beam.h) and libeilev_hip_prefix.so (rows that continue one
+shared prefix: prefix.o linked the same way, include/eilev_prefix.h) (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
 from __future__ import annotations
 
 import os
@@ -27,6 +28,9 @@ COMPANIONS = [  # (source, headers, export map, output)
 # libeilev_hip_t5beam.so needs the decoder's GEMVs, norms and attention launchers: its one unit is linked with the core library's objects
 # (no second compile of them); only eilev_t5beam_* is exported.  Not built for variants.
 T5BEAM = ("t5beam.hip", [os.path.join(_INC, "eilev_t5beam.h")], "exports_t5beam.map", "libeilev_hip_t5beam.so")
+# libeilev_hip_prefix.so: the same arrangement for prefix.hip (the OPT blocks around its own attention kernel); only eilev_prefix_* is exported
+PREFIX = ("prefix.hip", [os.path.join(_INC, "eilev_prefix.h")], "exports_prefix.map", "libeilev_hip_prefix.so")
+LINKED = (T5BEAM, PREFIX)  # (source, headers, export map, output): one unit each, linked with the core library's objects
 
 
 def _hipcc() -> str:
@@ -76,12 +80,14 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "", ext
         if not variant and (force or _stale(out, [src, emap] + [os.path.join(HERE, h) for h in hdr])):
             side_jobs.append([_hipcc(), *FLAGS, *extra_flags, "-shared", "-o", out, src, "-Wl,--version-script=" + emap])
 
-    tb_src, tb_obj, tb_map, tb_lib = (os.path.join(HERE, T5BEAM[0]), os.path.join(objdir, "t5beam.o"), os.path.join(HERE, T5BEAM[2]),
-                                      os.path.join(HERE, T5BEAM[3]))
-    if not variant and (force or _stale(tb_obj, [tb_src] + hdrs + [os.path.join(HERE, h) for h in T5BEAM[1]])):
-        jobs.append([_hipcc(), *FLAGS, *extra_flags, "-c", tb_src, "-o", tb_obj])
+    linked = []  # (object, export map, library) of the companions that carry the core library's objects
+    for src, hdr, emap, out in LINKED:
+        l_src, l_obj = os.path.join(HERE, src), os.path.join(objdir, src.replace(".hip", ".o"))
+        linked.append((l_obj, os.path.join(HERE, emap), os.path.join(HERE, out)))
+        if not variant and (force or _stale(l_obj, [l_src] + hdrs + [os.path.join(HERE, h) for h in hdr])):
+            jobs.append([_hipcc(), *FLAGS, *extra_flags, "-c", l_src, "-o", l_obj])
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(COMPANIONS) + 1) as ex:
+    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(COMPANIONS) + len(LINKED)) as ex:
         side_futs = [ex.submit(run, j) for j in side_jobs]
         for warn in ex.map(run, jobs):
             if verbose and warn.strip():
@@ -92,8 +98,9 @@ def build_hip(force: bool = False, verbose: bool = False, variant: str = "", ext
                 print(warn, file=sys.stderr)
     if force or jobs or _stale(lib, objs + [os.path.join(HERE, "exports.map")]):
         run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs, "-ldl", "-Wl,--version-script=" + os.path.join(HERE, "exports.map")])
-    if not variant and (force or _stale(tb_lib, objs + [tb_obj, tb_map])):
-        run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tb_lib, tb_obj, *objs, "-ldl", "-Wl,--version-script=" + tb_map])
+    for l_obj, l_map, l_lib in linked:
+        if not variant and (force or _stale(l_lib, objs + [l_obj, l_map])):
+            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", l_lib, l_obj, *objs, "-ldl", "-Wl,--version-script=" + l_map])
     return lib
 
 

@@ -9,14 +9,7 @@
 namespace {
 inline int64_t opt_ws_rows(int64_t M) { return (M > 16 && M < 32) ? 32 : M; }
 
-struct OptBufs {
-    bf16 *h, *x, *att, *qkv, *ffn;
-    int32_t *pid;
-    float *scratch;
-    uint8_t *a8;      // fp8 (e4m3) copy of the current linear's input rows (EilevOptWeights.w8_act_fp8)
-    float *a8_scale;  // one scale per row
-    size_t used;      // the bytes they take
-};
+}  // namespace
 
 // the buffers of M activation rows from `ws` (null: none)
 OptBufs carve_opt(const EilevDims *d, int64_t M, void *ws) {
@@ -35,7 +28,6 @@ OptBufs carve_opt(const EilevDims *d, int64_t M, void *ws) {
     b.used = cv.used;
     return b;
 }
-}  // namespace
 
 extern "C" size_t eilev_opt_workspace_bytes(const EilevDims *d, int64_t batch, int64_t seq_len) {
     return carve_opt(d, batch * (seq_len > 1 ? seq_len : 1), nullptr).used + 256;
@@ -70,8 +62,10 @@ int use_w8(GemmArgs &g, const EilevOptWeights *w, const uint8_t *w8, const float
     return EILEV_OK;
 }
 
+}  // namespace
+
 // q|k|v projection of x into b.qkv (q pre-scaled by head_dim^-0.5, hf modeling_opt.py:151)
-int opt_qkv(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s, int a_frag = 0) {
+int opt_qkv(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s, int a_frag) {
     const EilevOptLayer *L = &w->layers[l];
     const int D = d->t_hidden;
     const float scaling = 1.0f / sqrtf((float)(D / d->t_heads));
@@ -100,8 +94,8 @@ int opt_qkv(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &
 // final_layer_norm) — then b.x leaves as that LayerNorm of b.h, and both LayerNorms of the block ride on the split-K reductions of
 // out_proj / fc2 (GemmArgs::ln_out)
 // frag (decode steps of 17..32 rows, eilev_opt_decode_step): b.att, b.x and b.ffn in the row-block layout (common.h frag32_index); b.h stays row-major
-int opt_tail(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s, const void *next_ln_w = nullptr,
-             const void *next_ln_b = nullptr, int frag = 0, bool dry = false) {
+int opt_tail(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s, const void *next_ln_w,
+             const void *next_ln_b, int frag, bool dry) {
     const EilevOptLayer *L = &w->layers[l];
     const EilevOptLayerW8 *Q = w->layers_w8 ? &w->layers_w8[l] : nullptr;
     const int D = d->t_hidden, Ft = d->t_ffn;
@@ -132,6 +126,7 @@ int opt_tail(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs 
     return launch_gemm(g, 5, s);
 }
 
+namespace {
 // ---- small-batch decode (M <= 4 rows): the block as 5 launches of gemv.hip + the attention -------------------------------------------
 int g_decode_frag = 1;  // probe / test switch (eilev_debug_decode_frag, probe build): 0 = row-major activations in the 17..32-row decode step
 }  // namespace

@@ -111,5 +111,22 @@ int t5_decode_step_beam(const EilevT5Dims *d, const EilevT5Weights *w, const int
                         size_t workspace_bytes, void *stream);
 size_t t5_decode_step_beam_workspace_bytes(const EilevT5Dims *d, int64_t rows, int64_t enc_len, int64_t gen_capacity);
 
+// opt.hip: the parts of an OPT block around its attention, shared with prefix.hip (include/eilev_prefix.h: the same block over a shared prefix)
+struct OptBufs {
+    bf16 *h, *x, *att, *qkv, *ffn;
+    int32_t *pid;
+    float *scratch;
+    uint8_t *a8;      // fp8 (e4m3) copy of the current linear's input rows (EilevOptWeights.w8_act_fp8)
+    float *a8_scale;  // one scale per row
+    size_t used;      // the bytes they take
+};
+// the buffers of M activation rows from `ws` (null: none)
+OptBufs carve_opt(const EilevDims *d, int64_t M, void *ws);
+// q|k|v projection of b.x into b.qkv (q pre-scaled by head_dim^-0.5)
+int opt_qkv(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s, int a_frag = 0);
+// out_proj + residual, LN, fc1 + ReLU, fc2 + residual of block l: b.att, b.h -> b.h
+int opt_tail(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s, const void *next_ln_w = nullptr,
+             const void *next_ln_b = nullptr, int frag = 0, bool dry = false);
+
 // probe / test switches read outside the unit that defines them (set by eilev_debug_* of the probe build)
 extern int g_decode_rows;  // opt.hip; eilev_linear_rows (blocks.hip) follows it

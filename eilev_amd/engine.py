@@ -17,6 +17,14 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+class PrefixContext:
+    """A prefilled prefix that many rows continue (HipEngine.prefill_context): ``kv`` the OPT cache of ONE unpadded sequence with capacity
+    ``P``, ``last_logits`` (1, vocab) fp32 of its last position."""
+
+    def __init__(self, kv, P, last_logits):
+        self.kv, self.P, self.last_logits = kv, int(P), last_logits
+
+
 class HipEngine:
     """Runs the stages of VideoBlipForConditionalGeneration.forward/generate on gfx950 kernels."""
 
@@ -39,6 +47,8 @@ class HipEngine:
         self.timing = None  # bench.py sets this to a list to collect phase events
         self._decode_warm = False
         self._dec_cache = None  # most recent captured decode step + the buffers it is bound to
+        self._ctx_cache = None  # ... and that of greedy_decode_context (rows after a shared prefix)
+        self.context_stats = None    # per greedy_decode_context call: dict(path="shared", rows=, prefix=, new=, steps=)
         self.device_sampling = True  # generate(do_sample=True, num_beams=1): the draw runs in the captured step (sample_decode_device); False: the host loop
         self.sample_stats = None     # per sampling call: dict(path="device" | "host", steps=generated tokens per row)
         self.device_rules = True     # greedy / beam search with repetition_penalty, no_repeat_ngram_size, min_new_tokens or several EOS ids: the
@@ -182,7 +192,7 @@ class HipEngine:
         head = packed(self._keep["language_model.model.decoder.embed_tokens.weight"])
         abi.attach_opt_stream(self.pack, per_layer, head)
         self._stream_keep = keep
-        self._dec_cache = None  # a captured decode step holds the old pointers
+        self._dec_cache = self._ctx_cache = None  # a captured decode step holds the old pointers
         return bool(keep)
 
     def ensure_vit_fold(self):
@@ -591,34 +601,160 @@ class HipEngine:
                                             int(kv_capacity), _ptr(out), _ptr(ws), ws.numel(), self._stream()), "eilev_opt_extend")
         return out
 
-    def classify_loglik(self, prompt_embeds, prompt_mask, class_input_ids, class_attention_mask=None, class_batch_size=None):
+    def prefill_context(self, inputs_embeds):
+        """Prefill ONE unpadded sequence (1, P, Dt) into a cache of capacity P — the layout eilev_prefix_extend and the beam form of the decode
+        step read as a shared prefix.  Returns a PrefixContext: the cache, P and the last position's logits (1, vocab)."""
+        x = inputs_embeds.contiguous()
+        if x.dim() != 3 or x.shape[0] != 1 or x.shape[1] < 1:
+            raise ValueError(f"a context is one unpadded sequence (1, P, Dt), got {tuple(x.shape)}")
+        P = int(x.shape[1])
+        am = torch.ones((1, P), dtype=torch.int32, device=self.device)
+        last, _, kv = self.prefill(x, am, kv_capacity=P)
+        return PrefixContext(kv=kv, P=P, last_logits=last)
+
+    def extend_shared(self, ctx, new_embeds, kv_rows=None, cap=None, all_logits=False):
+        """``new_embeds`` (R, n, Dt) as positions P .. P + n - 1 of R rows that all continue the prefix ``ctx`` (eilev_prefix_extend: the prefix
+        cache is read once, never copied per row).  ``kv_rows``: a cache of ``new_kv_cache(R, cap)`` whose slots [0, n) receive the rows' new
+        K / V (None: none are written).  Returns fp32 logits: (R, vocab) of the last new position, or (R, n, vocab) with ``all_logits``.
+        Without ``kv_rows`` the rows run in parts where one call's limits (include/eilev_prefix.h) are exceeded."""
+        d = self.dims
+        px = abi.load_prefix()
+        x = new_embeds.contiguous()
+        R, n, _ = x.shape
+        if n > abi.PREFIX_MAX_NEW:
+            raise ValueError(f"at most {abi.PREFIX_MAX_NEW} new positions per row after a shared prefix, got {n}")
+        per = min(abi.PREFIX_MAX_ROWS, abi.PREFIX_MAX_STACKED // n)
+        if R > per and kv_rows is not None:
+            raise ValueError(f"at most {per} rows of {n} new positions per call when their K / V are kept")
+        out = torch.empty((R, n, d.vocab) if all_logits else (R, d.vocab), dtype=torch.float32, device=self.device)
+        for i in range(0, R, per):
+            r = min(per, R - i)
+            ws = self._workspace("prefix", px.eilev_prefix_workspace_bytes(C.byref(d), r, n))
+            abi.check(px.eilev_prefix_extend(C.byref(d), C.byref(self.pack.opt), _ptr(x[i:]), r, n, _ptr(ctx.kv), ctx.P, _ptr(kv_rows), int(cap or 0),
+                                             None if all_logits else _ptr(out[i:]), _ptr(out[i:]) if all_logits else None, _ptr(ws), ws.numel(),
+                                             self._stream()), "eilev_prefix_extend")
+        return out
+
+    def greedy_decode_context(self, ctx, new_embeds, max_new_tokens, eos_id=-1, pad_id=1, use_graph=True, trace=None, poll_every=8):
+        """Greedy decoding of R rows (R, n, Dt) that continue the prefix ``ctx``: extend_shared into a generation cache of capacity n +
+        max_new, the first token from eilev_greedy_select on its logits, then ONE captured step per token made of two existing entries —
+        eilev_opt_decode_step_beam with the R rows as R beams of one sample whose prompt cache is the prefix (identity ancestor table, its
+        counter preset to n + 1: position, KV slot and the number of visible generated keys all follow from that word, so the n new positions in
+        slots [0, n) are to it n tokens already generated) and eilev_greedy_select on a second counter.  The most recent graph is kept with
+        its buffers and reused by a call of the same shape on the same context.  ``trace``: a list that receives the extend's logits and every
+        eager step's; it turns capture off.  Returns int64 (R, steps) new tokens."""
+        from .sampling import eos_list
+
+        d = self.dims
+        R, n, _ = new_embeds.shape
+        if max_new_tokens <= 0:
+            return torch.empty((R, 0), dtype=torch.int64, device=self.device)
+        if R > 32:
+            if trace is not None:
+                raise ValueError("trace: at most 32 decode rows")
+            stats = []
+
+            def part(i, j):
+                ids = self.greedy_decode_context(ctx, new_embeds[i:j], max_new_tokens, eos_id, pad_id, use_graph, None, poll_every)
+                stats.append(self.context_stats["steps"])
+                return ids
+
+            out = self._chunked_rows(part, R, pad_id)
+            self.context_stats = dict(path="shared", rows=R, prefix=ctx.P, new=n, steps=max(stats))
+            return out
+        eos = eos_list(eos_id)
+        if len(eos) > 1:
+            raise NotImplementedError("greedy_decode_context takes one EOS id")
+        P, gen_cap, n_dec = ctx.P, n + max_new_tokens, max_new_tokens - 1
+        if n_dec > 0:
+            self.ensure_stream_layout(R)
+        graphable = use_graph and n_dec > 1 and trace is None
+        key = (ctx.kv.data_ptr(), P, R, n, max_new_tokens, tuple(eos), int(pad_id))
+        ent = self._ctx_cache if (graphable and self._ctx_cache is not None and self._ctx_cache["key"] == key) else None
+        if ent is None:
+            ent = dict(key=key, graph=None, ctx=ctx,  # (the entry keeps the context alive: its graph holds the prefix cache's address)
+                       kv_rows=self.new_kv_cache(R, gen_cap),
+                       am=torch.ones((1, P), dtype=torch.int32, device=self.device),
+                       n_valid=torch.full((R,), P, dtype=torch.int32, device=self.device),
+                       anc=torch.arange(R, dtype=torch.int32, device=self.device).repeat(gen_cap, 1).contiguous(),
+                       step_state=torch.zeros(2, dtype=torch.int32, device=self.device),  # the decode step's counter: tokens in the generation cache + 1
+                       sel_state=torch.zeros(2, dtype=torch.int32, device=self.device),   # the selection's: the output column, the rows left
+                       finished=torch.zeros(R, dtype=torch.uint8, device=self.device),
+                       tokens=torch.zeros(R, dtype=torch.int64, device=self.device),
+                       out=torch.empty((R, max_new_tokens), dtype=torch.int64, device=self.device),
+                       logits=torch.empty((R, d.vocab), dtype=torch.float32, device=self.device),
+                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), R, 1)))
+            if graphable:
+                self._ctx_cache = None
+                self._ctx_cache = ent
+        kv_rows, am, n_valid, anc, step_state, sel_state = ent["kv_rows"], ent["am"], ent["n_valid"], ent["anc"], ent["step_state"], ent["sel_state"]
+        finished, tokens, out, logits, ws = ent["finished"], ent["tokens"], ent["out"], ent["logits"], ent["ws"]
+        step_state.copy_(torch.tensor([n + 1, 0], dtype=torch.int32))
+        sel_state.zero_()
+        finished.zero_()
+        out.fill_(int(pad_id))
+        eos1 = eos[0] if eos else -1
+        last = self.extend_shared(ctx, new_embeds, kv_rows=kv_rows, cap=gen_cap)
+        if trace is not None:
+            trace.append(last.clone())
+        self._greedy_select(last, R, d.vocab, sel_state, finished, eos1, pad_id, tokens, out)
+
+        def one_step():
+            abi.check(self.lib.eilev_opt_decode_step_beam(
+                C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(step_state), _ptr(am), _ptr(n_valid), R, R, P, _ptr(ctx.kv), _ptr(kv_rows),
+                gen_cap, _ptr(anc), _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_opt_decode_step_beam")
+            self._greedy_select(logits, R, d.vocab, sel_state, finished, eos1, pad_id, tokens, out)
+
+        graph = ent["graph"] if graphable else None
+        if graphable and graph is None:  # (the warm run writes KV slot n of every row, as the first replay does)
+            graph = ent["graph"] = self._capture_step(one_step, (step_state, sel_state, finished, tokens, out), warm=True)
+        done = self._run_steps(n_dec, one_step, graph, sel_state, eos, poll_every, trace, logits)
+        self.context_stats = dict(path="shared", rows=R, prefix=P, new=n, steps=1 + done)
+        return self._trim_at_eos(out, 1 + done, eos)
+
+    def classify_loglik(self, prompt_embeds, prompt_mask, class_input_ids, class_attention_mask=None, class_batch_size=None,
+                        share_prompt_cache=False):
         """Mean log-likelihood of every class continuation after every prompt: (B, num_classes) fp32
-        [ref:eilev/model/v2.py:403-501].  The prompt is prefilled once; its KV cache is replicated per class chunk."""
+        [ref:eilev/model/v2.py:403-501].  The prompt is prefilled once; its KV cache is replicated per class chunk — or, with
+        ``share_prompt_cache``, stays ONE copy: each prompt row is stripped of its left padding, prefilled alone into a cache of its own
+        length and the classes run through extend_shared, which keeps no K / V of theirs."""
         d = self.dims
         B, L, _ = prompt_embeds.shape
         cls_ids = class_input_ids.to(self.device, torch.int64)
         n_cls, Lc = cls_ids.shape
         cls_mask = torch.ones_like(cls_ids) if class_attention_mask is None else class_attention_mask.to(self.device, torch.int64)
         pm = prompt_mask.to(self.device, torch.int32).contiguous()
-        cap = L + Lc
-        last, _, kv = self.prefill(prompt_embeds, pm, kv_capacity=cap)
-        planes = 2 * d.t_layers
         step = n_cls if class_batch_size is None else int(class_batch_size)
+        if share_prompt_cache:
+            ctxs = []
+            for b, nv in enumerate(pm.sum(dim=1).tolist()):
+                if nv < 1 or not bool(pm[b, L - nv:].all()):
+                    raise ValueError("share_prompt_cache takes left-padded prompts with at least one visible position")
+                ctxs.append(self.prefill_context(prompt_embeds[b:b + 1, L - nv:]))
+            last = torch.cat([c.last_logits for c in ctxs], dim=0)
+        else:
+            cap = L + Lc
+            last, _, kv = self.prefill(prompt_embeds, pm, kv_capacity=cap)
+        planes = 2 * d.t_layers
         cols = []
         for i in range(0, n_cls, step):
             ids, msk = cls_ids[i:i + step], cls_mask[i:i + step]
             nc = ids.shape[0]
             rows_ids = ids.unsqueeze(0).expand(B, -1, -1).reshape(B * nc, Lc)
             rows_msk = msk.unsqueeze(0).expand(B, -1, -1).reshape(B * nc, Lc)
-            full = torch.cat((pm.repeat_interleave(nc, dim=0), rows_msk.to(torch.int32)), dim=1)
-            kv_rows = kv.view(planes, B, -1).repeat_interleave(nc, dim=1).contiguous()
-            emb = self.embed_scatter(rows_ids, None, None)
-            logits = self.extend(emb, full, L, kv_rows, cap)
+            if share_prompt_cache:
+                emb = self.embed_scatter(ids, None, None)  # the classes' embeddings are the same after every prompt
+                logits = torch.cat([self.extend_shared(c, emb, all_logits=True) for c in ctxs], dim=0)
+            else:
+                full = torch.cat((pm.repeat_interleave(nc, dim=0), rows_msk.to(torch.int32)), dim=1)
+                kv_rows = kv.view(planes, B, -1).repeat_interleave(nc, dim=1).contiguous()
+                emb = self.embed_scatter(rows_ids, None, None)
+                logits = self.extend(emb, full, L, kv_rows, cap)
+                del kv_rows
             shift = torch.cat((last.repeat_interleave(nc, dim=0)[:, None], logits[:, :-1]), dim=1)
             labels = torch.where(rows_msk != 0, rows_ids, torch.full_like(rows_ids, -100))
             nll = self.ce_rows(shift.reshape(-1, d.vocab), labels.reshape(-1))
             cols.append(-nll.view(B, nc, Lc).sum(-1) / msk.sum(-1).unsqueeze(0).to(torch.float32))
-            del kv_rows
         return torch.cat(cols, dim=1)
 
     def greedy_decode(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, use_graph=True,

@@ -12,6 +12,8 @@ Not built (raise ``NotImplementedError``): contrastive / group-beam decoding (gr
 are).  ``generate`` takes ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_new_tokens`` and several EOS ids as numbers: greedy search, sampling and
 beam search apply them on the device in the decode step, for OPT and for flan-t5 (whose beam search runs on the device at head size 64, without
 copying or replicating a cache: include/eilev_t5beam.h); beam-search sampling and user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
+``encode_context`` prefills a leading part that many calls share — the in-context examples — once; ``generate(context=...)`` and
+``classify(share_prompt_cache=True)`` then run their rows over that one cached prefix (include/eilev_prefix.h; plain greedy search on OPT).
 ``output_hidden_states`` / ``output_attentions`` inside the full model's ``forward`` are served from slow paths for the vision wrapper,
 the Q-Former (self- and cross-attention weights), the OPT language model and the T5 stacks (hidden states; self- and cross-attention weights).  ``decoder_attention_mask`` with padding is honoured on the evaluation route (the first target position of a row must stay visible).
 """
@@ -193,6 +195,14 @@ class VideoBlipVisionModel(nn.Module):
         if return_dict is False:
             return (last, pooled, hidden, attn)  # fixed 4-tuple with None placeholders, as ref:eilev/model/v2.py:103
         return BaseModelOutputWithPooling(last_hidden_state=last, pooler_output=pooled, hidden_states=hidden, attentions=attn)
+
+
+class VideoContext:
+    """What ``encode_context`` returns and ``generate(context=...)`` takes: the prefilled prefix (its KV cache on the device, stored once),
+    the ids it was made from and its length ``P``.  Bound to the weights it was computed with: a parameter update makes it stale."""
+
+    def __init__(self, prefix, input_ids, key):
+        self.prefix, self.input_ids, self.P, self._key = prefix, input_ids, int(prefix.P), key
 
 
 def _params_key(module: nn.Module):
@@ -498,6 +508,7 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         if hasattr(self, "hf_device_map"):
             self._preprocess_accelerate()
         kw = dict(generate_kwargs)
+        context = kw.pop("context", None)  # a VideoContext: input_ids / pixel_values describe only what follows it
         num_beams = kw.pop("num_beams", 1)
         do_sample = kw.pop("do_sample", False)
         length_penalty = kw.pop("length_penalty", 1.0)  # only affects beam search
@@ -525,8 +536,9 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             elif self._is_t5:
                 max_new = int(max_len) - 1  # encoder-decoder: max_length counts the decoder tokens incl. the start token
             else:
-                max_new = int(max_len) - input_ids.shape[1]
+                max_new = int(max_len) - input_ids.shape[1] - (context.P if context is not None else 0)
         min_new = int(kw.pop("min_new_tokens", 0) or 0)
+        min_new_asked = min_new
         gen_cfg = getattr(self, "generation_config", None)
         eos = kw.pop("eos_token_id", getattr(gen_cfg, "eos_token_id", None) if gen_cfg is not None else None)
         if eos is None:
@@ -605,6 +617,23 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
                 raise NotImplementedError("prompt_lookup_num_tokens takes at most 8 EOS ids")
         if kw:
             raise NotImplementedError(f"unsupported generate() arguments on the HIP path: {sorted(kw)}")
+        if context is not None:  # v1: plain greedy search over a shared prefix; everything is checked here, before any encode
+            combo = [n for n, on in (("the flan-t5 language model (its encoder is bidirectional: a prefix cannot be cached)", self._is_t5),
+                                     ("num_beams > 1", num_beams > 1), ("do_sample=True", do_sample),
+                                     ("logits processors", len(procs) > 0 or bool(numbers)), ("stopping criteria", len(crit) > 0),
+                                     ("several EOS ids", len(eos_list(eos)) > 1), ("min_new_tokens", min_new_asked > 0),
+                                     ("output_scores / output_logits", want_scores or want_logits),
+                                     ("prompt_lookup_num_tokens", lookup is not None)) if on]
+            if combo:
+                raise NotImplementedError(f"generate(context=...) with {', '.join(combo)} is not built on the HIP path (plain greedy search only)")
+            if not isinstance(context, VideoContext):
+                raise TypeError("context must be what encode_context returned")
+            if input_ids is None or input_ids.dim() != 2:
+                raise ValueError("generate(context=...) takes input_ids (batch, seq_len): the query clip's slots and the question")
+            limit = self.config.text_config.max_position_embeddings
+            if context.P + input_ids.shape[1] + int(max_new) > limit:
+                raise ValueError(f"context ({context.P}) + input_ids ({input_ids.shape[1]}) + max_new_tokens ({int(max_new)}) exceed "
+                                 f"max_position_embeddings ({limit})")
         if want_dict and not (want_scores or want_logits):  # sequences only: any decoding mode, wrapped like hf wraps it
             from transformers.generation.utils import GenerateDecoderOnlyOutput, GenerateEncoderDecoderOutput
 
@@ -628,6 +657,8 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         eos1 = eos_ids[0] if eos_ids else -1
         with_rules = len(eos_ids) > 1 or min_new > 0 or rules is not None
         eng = self.engine()
+        if context is not None:
+            return self._generate_after_context(eng, context, emb, attention_mask, int(max_new), int(eos1), int(pad))
         if lookup is not None:  # the corpus: the row's visible text ids (no left padding, no video placeholder)
             keep = attention_mask[0] != 0
             if video_input_mask is not None:
@@ -675,15 +706,63 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         return eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad))
 
     @torch.no_grad()
+    def encode_context(self, input_ids, pixel_values=None, video_input_mask=None) -> VideoContext:
+        """Encode and prefill ONE unpadded row (1, P) — the in-context example clips and their texts — once.  The result serves any number
+        of ``generate(context=...)`` calls, whose arguments then describe only what follows it.  A parameter update makes it stale."""
+        if self._is_t5:
+            raise NotImplementedError("encode_context with the flan-t5 language model is not built: its encoder is bidirectional, so a prefix cannot "
+                                      "be cached")
+        if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1 or input_ids.shape[1] < 1:
+            raise ValueError("encode_context takes one unpadded row of input_ids, shape (1, P)")
+        if input_ids.shape[1] >= self.config.text_config.max_position_embeddings:
+            raise ValueError(f"a context of {input_ids.shape[1]} positions leaves no room below max_position_embeddings")
+        if pixel_values is not None:
+            assert video_input_mask is not None
+        from .. import abi
+
+        eng = self.engine()
+        if not abi.prefix_supported(eng.dims):
+            raise NotImplementedError("encode_context: the shared-prefix kernels take OPT head sizes 80 and 128")
+        emb, _, _ = self._encode(pixel_values, input_ids, video_input_mask)
+        return VideoContext(eng.prefill_context(emb), input_ids.clone(), self._hip[0])
+
+    def _generate_after_context(self, eng, context, emb, attention_mask, max_new, eos1, pad):
+        """Rows (B, S) after one context: grouped by visible length on the host, their left padding stripped, one greedy_decode_context call
+        per group; the new tokens in input order, padded with the pad id."""
+        if context._key != self._hip[0]:
+            raise ValueError("the context is stale: a parameter changed since encode_context")
+        B, S = attention_mask.shape
+        am = attention_mask.to("cpu") != 0
+        lens = am.sum(dim=1).tolist()
+        groups = {}
+        for b, n in enumerate(lens):
+            if n < 1 or not bool(am[b, S - n:].all()):
+                raise ValueError("generate(context=...) takes left-padded rows with at least one visible position")
+            groups.setdefault(n, []).append(b)
+        parts, steps = {}, 0
+        for n, rows in groups.items():
+            idx = torch.tensor(rows, device=emb.device)
+            parts[n] = eng.greedy_decode_context(context.prefix, emb.index_select(0, idx)[:, S - n:].contiguous(), max_new, eos_id=eos1, pad_id=pad)
+            steps = max(steps, eng.context_stats["steps"])
+        width = max(p.shape[1] for p in parts.values())
+        out = torch.full((B, width), pad, dtype=torch.int64, device=emb.device)
+        for n, rows in groups.items():
+            out[torch.tensor(rows, device=emb.device), : parts[n].shape[1]] = parts[n]
+        eng.context_stats = dict(path="shared", rows=B, prefix=context.P, new=max(groups), steps=steps)
+        return out
+
+    @torch.no_grad()
     def classify(self, prompt_input_ids, class_input_ids, prompt_attention_mask=None, pixel_values=None,
-                 prompt_video_input_mask=None, class_attention_mask=None, class_batch_size=None):
+                 prompt_video_input_mask=None, class_attention_mask=None, class_batch_size=None, share_prompt_cache=False):
         """Mean log-likelihood of each class text after each (left-padded) prompt: (batch, num_classes)
-        [ref:eilev/model/v2.py:326-501].  Prompt prefilled once on the HIP path, class tokens continue its KV cache."""
+        [ref:eilev/model/v2.py:326-501].  Prompt prefilled once on the HIP path, class tokens continue its KV cache — replicated per class,
+        or with ``share_prompt_cache=True`` read by every class from the one copy (include/eilev_prefix.h)."""
         assert self.config.use_decoder_only_language_model
         if pixel_values is not None:
             assert prompt_video_input_mask is not None
         emb, _, _ = self._encode(pixel_values, prompt_input_ids, prompt_video_input_mask)
         if prompt_attention_mask is None:
             prompt_attention_mask = torch.ones_like(prompt_input_ids)
-        ll = self.engine().classify_loglik(emb, prompt_attention_mask, class_input_ids, class_attention_mask, class_batch_size)
+        ll = self.engine().classify_loglik(emb, prompt_attention_mask, class_input_ids, class_attention_mask, class_batch_size,
+                                           share_prompt_cache=bool(share_prompt_cache))
         return ll.to(self.dtype)
