@@ -4,16 +4,9 @@
 // self/cross attention (:592-604; Sq=32, Skv=32 / T*257, d=64) and of OPTAttention prefill
 // (hf modeling_opt.py:163-176; causal, left/right padding mask, d=80), plus the single-query decode step.
 //
-// Prefill kernel: workgroup = 4 waves = 64 query rows of one (batch, head); K/V tiles of 64 keys are
-// staged in LDS (K row-major, V transposed).  Scores are computed TRANSPOSED, S^T = K Q^T, so that after
-// the 16x16x32 MFMA each lane owns one query row (col = lane & 15) and 16 of the tile's 64 keys: the
-// online-softmax statistics are per-lane scalars (+2 cross-lane-group shuffles) and the probabilities
-// are already in the B-operand layout of the second MFMA, O^T = V^T P^T (MFMA k-slots are an arbitrary
-// but consistent permutation of the keys) — no LDS round trip for P.  Head dims 64/80/88/128 are
-// zero-padded to DP in {64, 96, 128} on load.  fp32 softmax, bf16 P, fp32 accumulate.
-#include <type_traits>
-
-#include "common.h"
+// Prefill kernel (v1): the 64-query x 64-key flash tile of attn_tile64.h (S^T = K Q^T, lane = query row, P straight into O^T = V^T P^T)
+// over the key tiles a workgroup's 64 query rows can see.  Head dims 64/80/88/128 are zero-padded to DP in {64, 96, 128} on load.
+#include "attn_tile64.h"
 #include <type_traits>
 #include <utility>
 
@@ -32,17 +25,12 @@ namespace {
 
 template <int DP, bool DROP = false>  // DROP: dropout on the probabilities (training graph), compiled out of the inference kernel
 __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnArgs a) {
-    constexpr int KD = DP / 32;        // MFMA k-steps over the head dim
-    constexpr int DT = DP / 16;        // 16-row tiles of O^T
-    constexpr int CH = DP / 8;         // 16-byte chunks per K/V row
-    constexpr int KSTR = DP * 2 + 16;  // LDS row stride of the K tile (bytes): +16 keeps b128 reads conflict-free
-    constexpr int VSTR = 64 * 2 + 16;  // LDS row stride of the transposed V tile (64 keys per row)
-    __shared__ __attribute__((aligned(16))) char ks_[64 * KSTR];
-    __shared__ __attribute__((aligned(16))) char vt_[DP * VSTR];
+    using Tile = AttnTile64<DP>;
+    __shared__ __attribute__((aligned(16))) char ks_[Tile::KS_BYTES];
+    __shared__ __attribute__((aligned(16))) char vt_[Tile::VT_BYTES];
     __shared__ int msk_[64];
 
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int l15 = lane & 15, lg = lane >> 4;
+    const int tid = threadIdx.x, wid = tid >> 6, l15 = tid & 15;
     const int b = blockIdx.z, h = blockIdx.y;
     const int qrow = blockIdx.x * 64 + wid * 16 + l15;  // this lane's query row
     const int off = a.skv - a.sq;                        // causal offset: key j visible iff j <= i + off
@@ -52,17 +40,8 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnArgs a) {
     const bf16 *kp = a.k + (int64_t)b * a.k_bs + (int64_t)h * a.k_hs;
     const bf16 *vp = a.v + (int64_t)b * a.v_bs + (int64_t)h * a.v_hs;
 
-    bf16x8 qf[KD];
-#pragma unroll
-    for (int kd = 0; kd < KD; ++kd) {
-        const int d0 = kd * 32 + lg * 8;
-        qf[kd] = (qrow < a.sq && d0 < a.hd) ? *reinterpret_cast<const bf16x8 *>(qp + (int64_t)qrow * a.ldq + d0) : zero8();
-    }
-
-    float m_run = -1e30f, l_run = 0.0f;
-    f32x4 o[DT];
-#pragma unroll
-    for (int i = 0; i < DT; ++i) o[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    Tile t;
+    t.init(qrow < a.sq, qp + (int64_t)qrow * a.ldq, a.hd);
 
     int kv_end = a.skv;
     if (a.causal) {
@@ -70,127 +49,37 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnArgs a) {
         kv_end = min(a.skv, last_q + off + 1);
     }
 
+    const int last_key = a.causal ? qrow + off : INT_MAX - 1;  // the last key this lane's query may see
     for (int kv0 = 0; kv0 < kv_end; kv0 += 64) {
         __syncthreads();  // everyone is done reading the previous tile
-        // ---- stage K (row-major, coalesced 16-byte loads)
-        for (int id = tid; id < 64 * CH; id += 256) {
-            const int key = id / CH, c = id - key * CH;
-            const int gk = kv0 + key;
-            bf16x8 val = (gk < a.skv && c * 8 < a.hd) ? *reinterpret_cast<const bf16x8 *>(kp + (int64_t)gk * a.ldk + c * 8) : zero8();
-            *reinterpret_cast<bf16x8 *>(ks_ + key * KSTR + c * 16) = val;
-        }
-        // ---- stage V transposed: vt[d][key]
-        for (int id = tid; id < 64 * CH; id += 256) {
-            const int key = id & 63, c = id >> 6;
-            const int gk = kv0 + key;
-            bf16x8 val = (gk < a.skv && c * 8 < a.hd) ? *reinterpret_cast<const bf16x8 *>(vp + (int64_t)gk * a.ldv + c * 8) : zero8();
-#pragma unroll
-            for (int e = 0; e < 8; ++e) *reinterpret_cast<bf16 *>(vt_ + (c * 8 + e) * VSTR + key * 2) = val[e];
-        }
+        Tile::stage(ks_, vt_, kp, a.ldk, vp, a.ldv, kv0, a.skv, a.hd);
         if (tid < 64) {
             const int gk = kv0 + tid;
             int ok = gk < a.skv;
             if (ok && a.key_mask) ok = a.key_mask[(int64_t)b * a.mask_ld + gk] != 0;
-            msk_[tid] = ok;
+            msk_[tid] = ok ? gk : INT_MAX;  // the key's index, or one behind every last_key: visibility is ONE compare per score
         }
         __syncthreads();
-
-        // ---- S^T = K Q^T : st[ct][r] = S[q = l15][key = kv0 + ct*16 + lg*4 + r]
-        f32x4 st[4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-            st[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kd = 0; kd < KD; ++kd) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8 *>(ks_ + (ct * 16 + l15) * KSTR + (kd * 4 + lg) * 16);
-                st[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kd], st[ct], 0, 0, 0);
-            }
-        }
-        // ---- mask, online softmax (per-lane row statistics)
-        float mx = -1e30f;
-        bool okv[4][4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kl = ct * 16 + lg * 4 + r;
-                const bool ok = msk_[kl] != 0 && (!a.causal || (kv0 + kl) <= qrow + off);
-                okv[ct][r] = ok;
-                float s = st[ct][r] * sl2;
+        // (one compare per score and maps that capture by value keep a lane's 16 visibility masks scalar: profiles/attn_shared_step_resources.md)
+        t.step(
+            ks_, vt_, [=](int kl) { return msk_[kl] <= last_key; },
+            [=](int kl, float s) {
+                s *= sl2;
                 if (a.rel_tab) {  // T5 relative position bias, a function of (key - query position) per head
                     int ri = (kv0 + kl) - (qrow + off) + a.rel_off;
                     ri = ri < 0 ? 0 : (ri >= a.rel_n ? a.rel_n - 1 : ri);
                     s = fmaf(a.rel_tab[(int64_t)h * a.rel_hs + ri], 1.44269504088896340736f, s);
                 }
-                st[ct][r] = s;
-                if (ok) mx = fmaxf(mx, s);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = exp2f(m_run - m_new);
-        float rs = 0.0f;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = okv[ct][r] ? exp2f(st[ct][r] - m_new) : 0.0f;
-                st[ct][r] = p;
-                rs += p;
-                if (DROP) {  // training: the row sum keeps every probability, the product with V only the kept ones (scaled)
-                    const uint64_t idx = (((uint64_t)b * a.heads + h) * a.sq + qrow) * (uint64_t)a.skv + (kv0 + ct * 16 + lg * 4 + r);
-                    st[ct][r] = eilev_hash32(a.drop_seed, idx) >= a.drop_thr ? p * a.drop_scale : 0.0f;
-                }
-            }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int i = 0; i < DT; ++i) o[i] *= alpha;
-
-        // ---- O^T += V^T P^T.  k-slot (lg, j) of step ks  <->  key kv0 + 32 ks + (j < 4 ? lg*4 + j : 16 + lg*4 + j - 4)
-        bf16x8 pb[2];
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pb[ks2][j] = (bf16)st[2 * ks2][j];
-                pb[ks2][4 + j] = (bf16)st[2 * ks2 + 1][j];
-            }
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const char *vrow = vt_ + (dt * 16 + l15) * VSTR + lg * 8;
-#pragma unroll
-            for (int ks2 = 0; ks2 < 2; ++ks2) {
-                const bf16x4 lo = *reinterpret_cast<const bf16x4 *>(vrow + ks2 * 64);
-                const bf16x4 hi = *reinterpret_cast<const bf16x4 *>(vrow + ks2 * 64 + 32);
-                bf16x8 vf;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    vf[j] = lo[j];
-                    vf[4 + j] = hi[j];
-                }
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks2], o[dt], 0, 0, 0);
-            }
-        }
+                return s;
+            },
+            [=](int kl, float p) {
+                if (!DROP) return p;
+                // training: the row sum keeps every probability, the product with V only the kept ones (scaled)
+                const uint64_t idx = (((uint64_t)b * a.heads + h) * a.sq + qrow) * (uint64_t)a.skv + (kv0 + kl);
+                return eilev_hash32(a.drop_seed, idx) >= a.drop_thr ? p * a.drop_scale : 0.0f;
+            });
     }
-
-    // ---- finalize: o[dt][r] = O[q = l15][d = dt*16 + lg*4 + r]
-    if (qrow < a.sq) {
-        const float inv = l_run > 0.0f ? 1.0f / l_run : 0.0f;
-        bf16 *op = a.o + (int64_t)b * a.o_bs + (int64_t)h * a.o_hs + (int64_t)qrow * a.ldo;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const int d0 = dt * 16 + lg * 4;
-            if (d0 < a.hd) {
-                bf16x4 w;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) w[r] = (bf16)(o[dt][r] * inv);
-                *reinterpret_cast<bf16x4 *>(op + d0) = w;
-            }
-        }
-    }
+    if (qrow < a.sq) t.store(a.o + (int64_t)b * a.o_bs + (int64_t)h * a.o_hs + (int64_t)qrow * a.ldo, a.hd);
 }
 
 // ---------------------------------------------------------------------------------------------------------

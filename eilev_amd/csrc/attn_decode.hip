@@ -136,99 +136,142 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const bf16 *__re
     }
 }
 
+// ---- the register-resident key-range step of attn_decode1_kernel, attn_decode_part_kernel and attn_decode_loop_kernel, stated once -------------
+// A workgroup of THREADS threads owns a range of up to KEYS keys [k0, k1) of one (row, head).  Thread (kg, c) = (tid / NCH, tid % NCH) owns
+// 16-byte chunk c of keys k0 + kg, k0 + kg + G, ... (VK of them), all requested before anything is computed; thread t < KEYS owns key
+// k0 + t for the softmax.  P is rounded to bf16 for the product, the row sum comes from the unrounded values.  The members are the thread's
+// flash-decoding state (max, sum, its share of o): from the initial state ONE step leaves exactly the one-pass softmax (scale exp(-huge) = 0).
+template <int NCH, int VK, int THREADS, int KEYS>
+struct DecodeRange {
+    static constexpr int hd = NCH * 8, G = THREADS / NCH, NW = THREADS / 64;
+    static constexpr int RS = NCH + 1;  // row stride of the per-key chunk partials (odd: conflict-free column sums)
+    static constexpr int RED = KEYS * RS > G * hd ? KEYS * RS : G * hd;  // red[]: [key][chunk] score partials, afterwards the p . V partials [key group][hd]
+    static_assert(G * VK >= KEYS && KEYS <= THREADS, "every key of a range needs an owner");
+    float m = -1e30f, l = 0.0f, acc[8] = {};
+
+    // slot_new's row is `fresh` (the q|k|v row of this step), every other key's is row(key).  An index at or beyond k1 is clamped into the
+    // range; what it loads is never used.
+    template <class Row>
+    static __device__ __forceinline__ void load(bf16x8 (&r)[VK], int k0, int k1, int slot_new, const bf16 *fresh, Row row) {
+        const int c = threadIdx.x % NCH, kg = threadIdx.x / NCH;
+#pragma unroll
+        for (int i = 0; i < VK; ++i) {
+            int key = k0 + kg + i * G;
+            key = key < k1 ? key : k1 - 1;
+            r[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? fresh : row(key)) + c * 8);
+        }
+    }
+    // the last 2 NCH threads copy the new token's K / V (the q|k|v row of this step) into its cache slot (what a separate kv_write launch did)
+    static __device__ __forceinline__ void store_new(bf16 *kdst, bf16 *vdst, const bf16 *knew, const bf16 *vnew) {
+        const int t2 = threadIdx.x - (THREADS - 2 * NCH), which = t2 / NCH, cc = t2 - which * NCH;
+        if (t2 >= 0) *reinterpret_cast<bf16x8 *>((which ? vdst : kdst) + cc * 8) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
+    }
+    // One range into (m, l, acc).  q0 | q1: elements c * 8 .. c * 8 + 7 of the query; between() runs once the score partials are written (the
+    // loop kernel requests the next range's keys there); score_of(raw) is the score of key k0 + tid, -1e30 where it is not visible.  Ends
+    // with ps, red and wred still in use: a barrier before the next step.
+    template <class Between, class ScoreOf>
+    __device__ __forceinline__ void step(const bf16x8 (&kr)[VK], const bf16x8 (&vr)[VK], const float4 q0, const float4 q1, int k0, int k1, float *red, float *ps,
+                                         float *wred, Between between, ScoreOf score_of) {
+        const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, c = tid % NCH, kg = tid / NCH;
+        if (kg < G) {
+#pragma unroll
+            for (int i = 0; i < VK; ++i) {
+                const int kk = kg + i * G;
+                float kv[8];
+                unpack8(kr[i], kv);
+                if (kk < KEYS) red[kk * RS + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
+            }
+        }
+        between();
+        __syncthreads();
+        float s = -1e30f;
+        if (KEYS == THREADS || tid < KEYS) {
+            float a = 0.0f;
+#pragma unroll
+            for (int cc = 0; cc < NCH; ++cc) a += red[tid * RS + cc];
+            s = score_of(a);
+        }
+        const float mxw = wave_max(s);
+        if (lane == 0) wred[wid] = mxw;
+        __syncthreads();
+        float mx = wred[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) mx = fmaxf(mx, wred[w]);
+        const float m_new = fmaxf(m, mx);
+        const float p = s > -1e29f ? __expf(s - m_new) : 0.0f;
+        if (KEYS == THREADS || tid < KEYS) ps[tid] = (float)(bf16)p;
+        const float sw = wave_sum(p);
+        if (lane == 0) wred[NW + wid] = sw;
+        __syncthreads();  // (also: every thread has read its column of red[])
+        float rs = wred[NW];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) rs += wred[NW + w];
+        const float scale = __expf(m - m_new);
+        l = l * scale + rs;
+        m = m_new;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] *= scale;
+#pragma unroll
+        for (int i = 0; i < VK; ++i) {
+            const int kk = kg + i * G;
+            const float pj = (kk < KEYS && k0 + kk < k1) ? ps[kk] : 0.0f;
+            float vv[8];
+            unpack8(vr[i], vv);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
+        }
+    }
+    // the key groups' partial rows -> red[kg * hd + d] (a barrier inside); group_sum: their sum for output element d, in key-group order
+    __device__ __forceinline__ void put_partials(float *red) const {
+        const int c = threadIdx.x % NCH, kg = threadIdx.x / NCH;
+        if (kg < G) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) red[kg * hd + c * 8 + e] = acc[e];
+        }
+        __syncthreads();
+    }
+    static __device__ __forceinline__ float group_sum(const float *red, int d) {
+        float v = 0.0f;
+        for (int k2 = 0; k2 < G; ++k2) v += red[k2 * hd + d];
+        return v;
+    }
+};
+
 // ---- small-batch form (round 4): ONE workgroup per (row, head), every key in one pass, no partials, no merge -------------------------------
 // At batch 1 the split kernel above costs 13.9 us per block for 9.8 MB of keys and values (profiles/r04_decode_b1_kernel_stats.md): 128
 // workgroups each walk three dependent load rounds, and the merge of their partials was repeated by every workgroup of out_proj.  Here a
-// 1024-thread workgroup owns a head: thread j requests key j's whole row (NCH 16-byte loads) AND its share of V (thread (kg, c): chunk c of
-// keys kg, kg + G, ... — VK loads) before anything is computed, so the head's K and V (307 KB at 960 keys x 80) arrive in one round trip;
-// scores, a block-wide softmax (P rounded to bf16 for the product like every attention kernel here, the row sum from the unrounded
-// values), p . V through LDS partials, the normalised row straight to `out`.  The new token's K / V come from the q|k|v row and are
-// stored to the cache here (fuse_new of the split kernel).  Needs cap <= 1024 and cap <= VK * (1024 / NCH).
+// 1024-thread workgroup owns a head as ONE DecodeRange: the head's K and V (307 KB at 960 keys x 80) arrive in one round trip, the
+// normalised row goes straight to `out`; the new token's K / V come from the q|k|v row and are stored to the cache here (fuse_new of the
+// split kernel).  Needs cap <= 1024 and cap <= VK * (1024 / NCH).
 template <int NCH, int VK>
 __global__ __launch_bounds__(1024) void attn_decode1_kernel(const bf16 *__restrict__ qkv, bf16 *__restrict__ kc, bf16 *__restrict__ vc,
                                                             bf16 *__restrict__ out, const int32_t *__restrict__ attn_mask,
                                                             const int32_t *__restrict__ state, int seq_len, int cap, int heads, int64_t ldq) {
-    constexpr int hd = NCH * 8, G = 1024 / NCH, RS = NCH + 1;  // RS: row stride of the per-key chunk partials (odd: conflict-free column sums)
+    using R = DecodeRange<NCH, VK, 1024, 1024>;  // one range [0, kv_total), kv_total <= cap <= 1024 = KEYS (G * VK may exceed it: those owners idle)
+    constexpr int hd = R::hd, G = R::G;
     __shared__ __attribute__((aligned(16))) float qs[128];
     __shared__ float ps[1024];
     __shared__ float wred[32];
-    __shared__ float red[1024 * RS];  // scores: [key][chunk] partial dot products; afterwards the p . V partials [key group][hd] (G * hd <= 1024 * 8)
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ float red[R::RED];
+    const int tid = threadIdx.x, c = tid % NCH;
     const int h = blockIdx.x, b = blockIdx.y, d = heads * hd;
     const int kv_total = min(cap, seq_len + state[0]);
     const int slot_new = kv_total - 1;
     bf16 *kbase = kc + ((int64_t)b * heads + h) * cap * hd, *vbase = vc + ((int64_t)b * heads + h) * cap * hd;
     const bf16 *knew = qkv + (int64_t)b * ldq + d + h * hd, *vnew = knew + d;
-    // every load of the workgroup is requested here.  Thread (kg, c) owns 16-byte chunk c of keys kg, kg + G, ...: consecutive lanes read
-    // consecutive bytes (one key row per thread touches 64 cache lines per instruction and re-fetches each of them NCH times: 15 us)
-    const int c = tid % NCH, kg = tid / NCH;
+    // every load of the workgroup is requested here (one key row per thread instead would touch 64 cache lines per instruction and re-fetch
+    // each of them NCH times: 15 us)
     bf16x8 kr[VK], vr[VK];
-#pragma unroll
-    for (int i = 0; i < VK; ++i) {
-        int key = kg + i * G;
-        key = key < kv_total ? key : slot_new;
-        kr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? knew : kbase + (int64_t)key * hd) + c * 8);
-    }
-#pragma unroll
-    for (int i = 0; i < VK; ++i) {
-        int key = kg + i * G;
-        key = key < kv_total ? key : slot_new;
-        vr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? vnew : vbase + (int64_t)key * hd) + c * 8);
-    }
+    R::load(kr, 0, kv_total, slot_new, knew, [&](int key) { return kbase + (int64_t)key * hd; });
+    R::load(vr, 0, kv_total, slot_new, vnew, [&](int key) { return vbase + (int64_t)key * hd; });
     const bool vis = tid < kv_total && (tid >= seq_len || !attn_mask || attn_mask[(int64_t)b * seq_len + tid] != 0);
     if (tid < hd) qs[tid] = (float)qkv[(int64_t)b * ldq + h * hd + tid];
-    if (tid >= 1024 - 2 * NCH) {  // the new token's K / V -> the cache (what a separate kv_write launch did)
-        const int t2 = tid - (1024 - 2 * NCH), which = t2 / NCH, cc = t2 - which * NCH;
-        *reinterpret_cast<bf16x8 *>((which ? vbase : kbase) + (int64_t)slot_new * hd + cc * 8) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
-    }
+    R::store_new(kbase + (int64_t)slot_new * hd, vbase + (int64_t)slot_new * hd, knew, vnew);
     __syncthreads();
-    if (kg < G) {
-        const float4 q0 = *reinterpret_cast<const float4 *>(&qs[c * 8]), q1 = *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]);
-#pragma unroll
-        for (int i = 0; i < VK; ++i) {
-            const int key = kg + i * G;
-            float kv[8];
-            unpack8(kr[i], kv);
-            if (key < 1024)
-                red[key * RS + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
-        }
-    }
-    __syncthreads();
-    float s = 0.0f;
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc) s += red[tid * RS + cc];
-    s = vis ? s : -1e30f;
-    const float mxw = wave_max(s);
-    if (lane == 0) wred[wid] = mxw;
-    __syncthreads();
-    float mx = wred[0];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) mx = fmaxf(mx, wred[w]);
-    const float p = s > -1e29f ? __expf(s - mx) : 0.0f;
-    ps[tid] = (float)(bf16)p;
-    const float sw = wave_sum(p);
-    if (lane == 0) wred[16 + wid] = sw;
-    __syncthreads();  // (also: every thread has read its red[] column sums)
-    float lsum = 0.0f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) lsum += wred[16 + w];
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < VK; ++i) {
-        const int key = kg + i * G;
-        const float pj = key < kv_total ? ps[key < 1024 ? key : 1023] : 0.0f;
-        float vv[8];
-        unpack8(vr[i], vv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
-    }
-    if (kg < G) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[kg * hd + c * 8 + e] = acc[e];
-    }
-    __syncthreads();
+    R r;
+    r.step(kr, vr, *reinterpret_cast<const float4 *>(&qs[c * 8]), *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]), 0, kv_total, red, ps, wred, [] {},
+           [&](float a) { return vis ? a : -1e30f; });
+    r.put_partials(red);
     // G partial rows -> one: two levels (a single thread per output element walking all G partials is a chain of G dependent LDS reads:
     // ~5 us of the 12 this kernel took)
     constexpr int P2 = 1024 / hd;  // threads per output element in the first level
@@ -243,11 +286,11 @@ __global__ __launch_bounds__(1024) void attn_decode1_kernel(const bf16 *__restri
         float v = 0.0f;
 #pragma unroll
         for (int jj = 0; jj < P2; ++jj) v += ps[jj * hd + tid];
-        out[((int64_t)b * heads + h) * hd + tid] = (bf16)(lsum > 0.0f ? v / lsum : 0.0f);
+        out[((int64_t)b * heads + h) * hd + tid] = (bf16)(r.l > 0.0f ? v / r.l : 0.0f);
     }
 }
 
-// The same loading scheme over a RANGE of keys: 256 threads own keys [128 sp, 128 sp + 128) of one (row, head) and leave the un-normalised
+// DecodeRange over a RANGE of keys: 256 threads own keys [128 sp, 128 sp + 128) of one (row, head) and leave the un-normalised
 // partial (max, sum, o[hd]) in `part` — the flash-decoding format of attn_decode_split_kernel, merged by the consumer (gemv1_kernel's prologue
 // of out_proj).  One workgroup per head pulls 307 KB through ONE CU (12.1 us at batch 1); 8 splits put 38 KB on each of 256 CUs.
 // BEAM (r4, eilev_opt_decode_step_beam at <= 8 rows of head size 80): the addressing of attn_decode_split_kernel's beam form — keys below
@@ -260,13 +303,13 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16 *__res
                                                                const int32_t *__restrict__ state, int seq_len, int cap, int heads, int64_t ldq,
                                                                bf16 *__restrict__ kg_ = nullptr, bf16 *__restrict__ vg_ = nullptr,
                                                                const int32_t *__restrict__ anc = nullptr, int beams = 1, int cap_g = 0, int rows = 0) {
-    constexpr int hd = NCH * 8, G = 256 / NCH, RS = NCH + 1;
-    static_assert(G * VK >= KEYS && KEYS <= 256, "every key of the range needs an owner");
+    using R = DecodeRange<NCH, VK, 256, KEYS>;
+    constexpr int hd = R::hd;
     __shared__ __attribute__((aligned(16))) float qs[128];
     __shared__ float ps[KEYS];
     __shared__ float wred[8];
-    __shared__ float red[KEYS * RS > G * hd ? KEYS * RS : G * hd];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ float red[R::RED];
+    const int tid = threadIdx.x, c = tid % NCH;
     const int h = blockIdx.x, b = blockIdx.y, sp = blockIdx.z, nsplit = gridDim.z, d = heads * hd;
     const int kv_total = BEAM ? min(seq_len + cap_g, seq_len + state[0]) : min(cap, seq_len + state[0]);
     // (beam form: a caller that passes a step count of 0, or more than the generation cache holds, must not make this row write outside its slots)
@@ -283,93 +326,37 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16 *__res
     const int srow = BEAM ? b / beams : b;  // row of the prompt cache and of the attention mask
     bf16 *kbase = kc + ((int64_t)srow * heads + h) * cap * hd, *vbase = vc + ((int64_t)srow * heads + h) * cap * hd;
     const bf16 *knew = qkv + (int64_t)b * ldq + d + h * hd, *vnew = knew + d;
+    const int64_t rows_w = rows, heads_w = heads, cap_gw = cap_g;  // (widened once: the 12 row addresses of a thread share them)
     auto key_row = [&](const bf16 *base, const bf16 *gen, int j) -> const bf16 * {
         if (!BEAM || j < seq_len) return base + (int64_t)j * hd;
         const int gi = j - seq_len;
-        int a = anc[(int64_t)gi * rows + b];  // (an entry outside [0, rows) must not become an address)
+        int a = anc[gi * rows_w + b];  // (an entry outside [0, rows) must not become an address)
         a = a < 0 ? 0 : (a >= rows ? rows - 1 : a);
-        return gen + (((int64_t)a * heads + h) * cap_g + gi) * hd;
+        return gen + ((a * heads_w + h) * cap_gw + gi) * hd;
     };
-    const int c = tid % NCH, kg = tid / NCH;
     bf16x8 kr[VK], vr[VK];
-#pragma unroll
-    for (int i = 0; i < VK; ++i) {
-        int key = k0 + kg + i * G;
-        key = key < k1 ? key : k1 - 1;
-        kr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? knew : key_row(kbase, kg_, key)) + c * 8);
-    }
-#pragma unroll
-    for (int i = 0; i < VK; ++i) {
-        int key = k0 + kg + i * G;
-        key = key < k1 ? key : k1 - 1;
-        vr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? vnew : key_row(vbase, vg_, key)) + c * 8);
-    }
+    R::load(kr, k0, k1, slot_new, knew, [&](int key) { return key_row(kbase, kg_, key); });
+    R::load(vr, k0, k1, slot_new, vnew, [&](int key) { return key_row(vbase, vg_, key); });
     const int jt = k0 + tid;  // thread t < KEYS owns key k0 + t for the softmax
     const bool vis = tid < KEYS && jt < k1 && (jt >= seq_len || !attn_mask || attn_mask[(int64_t)srow * seq_len + jt] != 0);
     if (tid < hd) qs[tid] = (float)qkv[(int64_t)b * ldq + h * hd + tid];
-    if (slot_new >= k0 && slot_new < k1 && tid >= 256 - 2 * NCH) {  // the split that owns the newest slot stores it to the cache
-        const int t2 = tid - (256 - 2 * NCH), which = t2 / NCH, cc = t2 - which * NCH;
-        bf16 *dst = BEAM ? (which ? vg_ : kg_) + (((int64_t)b * heads + h) * cap_g + (slot_new - seq_len)) * hd : (which ? vbase : kbase) + (int64_t)slot_new * hd;
-        *reinterpret_cast<bf16x8 *>(dst + cc * 8) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
+    if (slot_new >= k0 && slot_new < k1) {  // the split that owns the newest slot stores it to the cache
+        const int64_t at = BEAM ? (((int64_t)b * heads + h) * cap_g + (slot_new - seq_len)) * hd : (int64_t)slot_new * hd;
+        R::store_new((BEAM ? kg_ : kbase) + at, (BEAM ? vg_ : vbase) + at, knew, vnew);
     }
     __syncthreads();
-    if (kg < G) {
-        const float4 q0 = *reinterpret_cast<const float4 *>(&qs[c * 8]), q1 = *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]);
-#pragma unroll
-        for (int i = 0; i < VK; ++i) {
-            const int kk = kg + i * G;
-            float kv[8];
-            unpack8(kr[i], kv);
-            if (kk < KEYS) red[kk * RS + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
-        }
-    }
-    __syncthreads();
-    float s = -1e30f;
-    if (tid < KEYS) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int cc = 0; cc < NCH; ++cc) acc += red[tid * RS + cc];
-        s = vis ? acc : -1e30f;
-    }
-    const float mxw = wave_max(s);
-    if (lane == 0) wred[wid] = mxw;
-    __syncthreads();
-    const float mx = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
-    const float p = s > -1e29f ? __expf(s - mx) : 0.0f;
-    if (tid < KEYS) ps[tid] = (float)(bf16)p;
-    const float sw = wave_sum(p);
-    if (lane == 0) wred[4 + wid] = sw;
-    __syncthreads();
-    const float lsum = wred[4] + wred[5] + wred[6] + wred[7];
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < VK; ++i) {
-        const int kk = kg + i * G;
-        const float pj = (kk < KEYS && k0 + kk < k1) ? ps[kk] : 0.0f;
-        float vv[8];
-        unpack8(vr[i], vv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
-    }
-    if (kg < G) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[kg * hd + c * 8 + e] = acc[e];
-    }
-    __syncthreads();
-    if (tid < hd) {
-        float v = 0.0f;
-        for (int k2 = 0; k2 < G; ++k2) v += red[k2 * hd + tid];
-        po[2 + tid] = v;
-    }
+    R r;
+    r.step(kr, vr, *reinterpret_cast<const float4 *>(&qs[c * 8]), *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]), k0, k1, red, ps, wred, [] {},
+           [&](float a) { return vis ? a : -1e30f; });
+    r.put_partials(red);
+    if (tid < hd) po[2 + tid] = R::group_sum(red, tid);
     if (tid == 0) {
-        po[0] = mx;
-        po[1] = lsum;
+        po[0] = r.m;
+        po[1] = r.l;
     }
 }
 
-// ---- (round 5) any batch size: ONE workgroup per (row, head) walks the head's keys in ranges of KEYS with the loading scheme above ---------
+// ---- (round 5) any batch size: ONE workgroup per (row, head) walks the head's keys in ranges of KEYS (DecodeRange) ----------------------
 // At batch 32 the 128-key ranges were 8192 workgroups + a merge launch (60.7 + 6.4 us per block), 256-key ranges 4096 + 5.0 us.  Here the
 // 256 threads of a workgroup keep the flash-decoding state (max, sum, o) in registers across the ranges — the online form of the merge
 // kernel's arithmetic — and request range r + 1's keys as soon as range r's scores exist (its values after p . V): no partials, no merge
@@ -383,111 +370,48 @@ __global__ __launch_bounds__(256) void attn_decode_loop_kernel(const bf16 *__res
                                                                int64_t rel_hs = 0, int rel_off = 0) {
     // state == nullptr: kv_total = seq_len, given by the host (the flan-t5 cross-attention: keys = encoder positions, attn_mask = their
     // padding mask, q rows of stride ldq); fuse_new == 0: every key is in the cache already
-    constexpr int hd = NCH * 8, G = 256 / NCH, RS = NCH + 1;
-    static_assert(G * VK >= KEYS && KEYS <= 256, "every key of a range needs an owner");
+    using R = DecodeRange<NCH, VK, 256, KEYS>;
+    constexpr int hd = R::hd;
     __shared__ __attribute__((aligned(16))) float qs[128];
     __shared__ float ps[KEYS];
     __shared__ float wred[8];
-    __shared__ float red[KEYS * RS > G * hd ? KEYS * RS : G * hd];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ float red[R::RED];
+    const int tid = threadIdx.x, c = tid % NCH;
     const int h = blockIdx.x, b = blockIdx.y, d = heads * hd;
     const int kv_total = min(cap, seq_len + (state ? state[0] : 0));
     const int slot_new = fuse_new ? kv_total - 1 : -1;
     bf16 *kbase = kc + ((int64_t)b * heads + h) * cap * hd, *vbase = vc + ((int64_t)b * heads + h) * cap * hd;
     const bf16 *knew = qkv + (int64_t)b * ldq + d + h * hd, *vnew = knew + d;
-    const int c = tid % NCH, kg = tid / NCH;
     bf16x8 kr[VK], vr[VK];
-    auto load_k = [&](int k0) {
-        const int k1 = min(kv_total, k0 + KEYS);
-#pragma unroll
-        for (int i = 0; i < VK; ++i) {
-            int key = k0 + kg + i * G;
-            key = key < k1 ? key : k1 - 1;
-            kr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? knew : kbase + (int64_t)key * hd) + c * 8);
-        }
-    };
-    auto load_v = [&](int k0) {
-        const int k1 = min(kv_total, k0 + KEYS);
-#pragma unroll
-        for (int i = 0; i < VK; ++i) {
-            int key = k0 + kg + i * G;
-            key = key < k1 ? key : k1 - 1;
-            vr[i] = *reinterpret_cast<const bf16x8 *>((key == slot_new ? vnew : vbase + (int64_t)key * hd) + c * 8);
-        }
-    };
+    auto load_k = [&](int k0) { R::load(kr, k0, min(kv_total, k0 + KEYS), slot_new, knew, [&](int key) { return kbase + (int64_t)key * hd; }); };
+    auto load_v = [&](int k0) { R::load(vr, k0, min(kv_total, k0 + KEYS), slot_new, vnew, [&](int key) { return vbase + (int64_t)key * hd; }); };
     load_k(0);
     load_v(0);
     if (tid < hd) qs[tid] = (float)qkv[(int64_t)b * ldq + h * hd + tid];
-    if (fuse_new && tid >= 256 - 2 * NCH) {  // the newest key / value: from the q|k|v row of this step into the cache (fuse_new of the split kernel)
-        const int t2 = tid - (256 - 2 * NCH), which = t2 / NCH, cc = t2 - which * NCH;
-        bf16 *dst = (which ? vbase : kbase) + (int64_t)slot_new * hd;
-        *reinterpret_cast<bf16x8 *>(dst + cc * 8) = *reinterpret_cast<const bf16x8 *>((which ? vnew : knew) + cc * 8);
-    }
+    if (fuse_new) R::store_new(kbase + (int64_t)slot_new * hd, vbase + (int64_t)slot_new * hd, knew, vnew);  // (fuse_new of the split kernel)
     __syncthreads();
     const float4 q0 = *reinterpret_cast<const float4 *>(&qs[c * 8]), q1 = *reinterpret_cast<const float4 *>(&qs[c * 8 + 4]);
-    float m_run = -1e30f, l_run = 0.0f;
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+    R r;
     for (int k0 = 0; k0 < kv_total; k0 += KEYS) {
         const int k1 = min(kv_total, k0 + KEYS);
-        if (kg < G) {
-#pragma unroll
-            for (int i = 0; i < VK; ++i) {
-                const int kk = kg + i * G;
-                float kv[8];
-                unpack8(kr[i], kv);
-                if (kk < KEYS) red[kk * RS + c] = kv[0] * q0.x + kv[1] * q0.y + kv[2] * q0.z + kv[3] * q0.w + kv[4] * q1.x + kv[5] * q1.y + kv[6] * q1.z + kv[7] * q1.w;
-            }
-        }
-        if (k0 + KEYS < kv_total) load_k(k0 + KEYS);  // (uniform) the next range's keys: in flight under this range's softmax and p . V
-        __syncthreads();
-        const int jt = k0 + tid;
-        float s = -1e30f;
-        if (tid < KEYS && jt < k1 && (jt >= seq_len || !attn_mask || attn_mask[(int64_t)b * seq_len + jt] != 0)) {
-            float a = 0.0f;
-#pragma unroll
-            for (int cc = 0; cc < NCH; ++cc) a += red[tid * RS + cc];
-            // (flan-t5 self-attention: per-head position bias over key - query position, the query at kv_total - 1; rel_off < 0: the table of this query row)
-            if (rel_tab) a += rel_tab[(int64_t)h * rel_hs + (rel_off >= 0 ? (jt - (kv_total - 1)) + rel_off : jt)];
-            s = a;
-        }
-        const float mxw = wave_max(s);
-        if (lane == 0) wred[wid] = mxw;
-        __syncthreads();
-        const float m_new = fmaxf(m_run, fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3])));
-        const float p = s > -1e29f ? __expf(s - m_new) : 0.0f;
-        if (tid < KEYS) ps[tid] = (float)(bf16)p;  // P rounded to bf16 for the product like every attention kernel here; the row sum from the unrounded values
-        const float sw = wave_sum(p);
-        if (lane == 0) wred[4 + wid] = sw;
-        __syncthreads();
-        const float scale = __expf(m_run - m_new);  // first range: exp(-huge) = 0 (and the state it scales is 0)
-        l_run = l_run * scale + (wred[4] + wred[5] + wred[6] + wred[7]);
-        m_run = m_new;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] *= scale;
-#pragma unroll
-        for (int i = 0; i < VK; ++i) {
-            const int kk = kg + i * G;
-            const float pj = (kk < KEYS && k0 + kk < k1) ? ps[kk] : 0.0f;
-            float vv[8];
-            unpack8(vr[i], vv);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += pj * vv[e];
-        }
+        // (uniform) the next range's keys are requested as soon as this range's are consumed: in flight under its softmax and p . V
+        r.step(
+            kr, vr, q0, q1, k0, k1, red, ps, wred, [&] { if (k0 + KEYS < kv_total) load_k(k0 + KEYS); },
+            [&](float a) {
+                const int jt = k0 + tid;
+                if (jt >= k1 || !(jt >= seq_len || !attn_mask || attn_mask[(int64_t)b * seq_len + jt] != 0)) return -1e30f;
+                // (flan-t5 self-attention: per-head position bias over key - query position, the query at kv_total - 1; rel_off < 0: the table of this query row)
+                if (rel_tab) a += rel_tab[(int64_t)h * rel_hs + (rel_off >= 0 ? (jt - (kv_total - 1)) + rel_off : jt)];
+                return a;
+            });
         if (k0 + KEYS < kv_total) load_v(k0 + KEYS);
         __syncthreads();  // ps / red / wred are rewritten by the next range
     }
-    if (kg < G) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[kg * hd + c * 8 + e] = acc[e];
-    }
-    __syncthreads();
+    r.put_partials(red);
     if (tid < hd) {
-        float v = 0.0f;
-        for (int k2 = 0; k2 < G; ++k2) v += red[k2 * hd + tid];
+        const float v = R::group_sum(red, tid);
         // out_frag: the row-block layout out_proj's GEMV reads at 17..32 rows (common.h frag32_index)
-        out[out_frag ? frag32_index(b, h * hd + tid) : ((int64_t)b * heads + h) * hd + tid] = (bf16)(l_run > 0.0f ? v / l_run : 0.0f);
+        out[out_frag ? frag32_index(b, h * hd + tid) : ((int64_t)b * heads + h) * hd + tid] = (bf16)(r.l > 0.0f ? v / r.l : 0.0f);
     }
 }
 

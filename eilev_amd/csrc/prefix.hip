@@ -3,11 +3,9 @@
 // core library's objects.
 //
 // prefix_attn_kernel.  The rows * new_len queries are STACKED along the MFMA M dimension (stacked index s = r * new_len + t), a workgroup
-// of 4 waves owns 64 of them for one head — with a small new_len (classify(): 2..8 tokens per class) a tile spans many rows.  The frame is
-// attn_prefill_kernel's (attention.hip): K / V tiles of 64 keys staged in LDS (K row-major, V transposed, head sizes 80 / 128 zero-padded to
-// DP = 96 / 128), S^T = K Q^T on the 16x16x32 MFMA so that a lane owns one query and its online-softmax statistics, P already in the
-// B-operand layout of O^T = V^T P^T; scores in fp32, P rounded to bf16 for the product, the row sum from the unrounded P, O / l rounded to
-// bf16 once, a query without a visible key writes zeros.  Two phases over one running (max, sum, O):
+// of 4 waves owns 64 of them for one head — with a small new_len (classify(): 2..8 tokens per class) a tile spans many rows.  The tile step
+// and its arithmetic are attn_tile64.h's, shared with attn_prefill_kernel (head sizes 80 / 128 zero-padded to DP = 96 / 128).  Two phases
+// over one running (max, sum, O):
 //   1. the prefix key tiles [0, P) from the cache planes [heads][prefix_cap][hd]: every query sees every one of them — no mask beyond
 //      "the key exists" (slots at or beyond P are never loaded: the tile holds zeros there and the score is dropped);
 //   2. the window of stacked NEW keys that covers the tile's rows, [first row of the tile * new_len, last query of the tile], read from
@@ -15,6 +13,7 @@
 //      are worked out once per tile into LDS).
 // No per-row cache is ever read.  Every global read is guarded by an index check; the only writes go to `out`, rows < rows * new_len.
 #include "../../include/eilev_prefix.h"
+#include "attn_tile64.h"
 #include "stages.h"
 
 namespace {
@@ -30,127 +29,32 @@ struct PrefixAttnArgs {
 
 template <int DP>
 __global__ __launch_bounds__(256) void prefix_attn_kernel(const PrefixAttnArgs a) {
-    constexpr int KD = DP / 32;        // MFMA k-steps over the head dim
-    constexpr int DT = DP / 16;        // 16-row tiles of O^T
-    constexpr int CH = DP / 8;         // 16-byte chunks per K/V row
-    constexpr int KSTR = DP * 2 + 16;  // LDS row stride of the K tile (bytes): +16 keeps b128 reads conflict-free
-    constexpr int VSTR = 64 * 2 + 16;  // LDS row stride of the transposed V tile (64 keys per row)
-    __shared__ __attribute__((aligned(16))) char ks_[64 * KSTR];
-    __shared__ __attribute__((aligned(16))) char vt_[DP * VSTR];
+    using Tile = AttnTile64<DP>;
+    __shared__ __attribute__((aligned(16))) char ks_[Tile::KS_BYTES];
+    __shared__ __attribute__((aligned(16))) char vt_[Tile::VT_BYTES];
     __shared__ int krow_[64];  // phase 2: the row a tile's key belongs to, -1 where the tile has no key
 
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int l15 = lane & 15, lg = lane >> 4;
+    const int tid = threadIdx.x, wid = tid >> 6, l15 = tid & 15;
     const int h = blockIdx.y;
     const int s0 = blockIdx.x * 64;
     const int qs = s0 + wid * 16 + l15;  // this lane's stacked query
     const int qr = qs / a.n;             // ... and its row
     const float sl2 = a.scale * 1.44269504088896340736f;
 
-    bf16x8 qf[KD];
-#pragma unroll
-    for (int kd = 0; kd < KD; ++kd) {
-        const int d0 = kd * 32 + lg * 8;
-        qf[kd] = (qs < a.S && d0 < a.hd) ? *reinterpret_cast<const bf16x8 *>(a.q + (int64_t)qs * a.ldq + h * a.hd + d0) : zero8();
-    }
-
-    float m_run = -1e30f, l_run = 0.0f;
-    f32x4 o[DT];
-#pragma unroll
-    for (int i = 0; i < DT; ++i) o[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    Tile t;
+    t.init(qs < a.S, a.q + (int64_t)qs * a.ldq + h * a.hd, a.hd);
 
     // one tile of 64 keys [k0, k0 + 64) n [0, kend) of the key rows kb / vb (row strides ldk / ldv); NEW: the stacked new keys
     auto tile = [&](auto new_tag, const bf16 *kb, int64_t ldk, const bf16 *vb, int64_t ldv, int k0, int kend) {
         constexpr bool NEW = decltype(new_tag)::value;
         __syncthreads();  // everyone is done reading the previous tile
-        // ---- stage K (row-major, coalesced 16-byte loads)
-        for (int id = tid; id < 64 * CH; id += 256) {
-            const int key = id / CH, c = id - key * CH;
-            const int gk = k0 + key;
-            bf16x8 val = (gk < kend && c * 8 < a.hd) ? *reinterpret_cast<const bf16x8 *>(kb + (int64_t)gk * ldk + c * 8) : zero8();
-            *reinterpret_cast<bf16x8 *>(ks_ + key * KSTR + c * 16) = val;
-        }
-        // ---- stage V transposed: vt[d][key]
-        for (int id = tid; id < 64 * CH; id += 256) {
-            const int key = id & 63, c = id >> 6;
-            const int gk = k0 + key;
-            bf16x8 val = (gk < kend && c * 8 < a.hd) ? *reinterpret_cast<const bf16x8 *>(vb + (int64_t)gk * ldv + c * 8) : zero8();
-#pragma unroll
-            for (int e = 0; e < 8; ++e) *reinterpret_cast<bf16 *>(vt_ + (c * 8 + e) * VSTR + key * 2) = val[e];
-        }
+        Tile::stage(ks_, vt_, kb, ldk, vb, ldv, k0, kend, a.hd);
         if (NEW && tid < 64) krow_[tid] = k0 + tid < kend ? (k0 + tid) / a.n : -1;
         __syncthreads();
-
-        // ---- S^T = K Q^T : st[ct][r] = S[q = l15][key = k0 + ct*16 + lg*4 + r]
-        f32x4 st[4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-            st[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kd = 0; kd < KD; ++kd) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8 *>(ks_ + (ct * 16 + l15) * KSTR + (kd * 4 + lg) * 16);
-                st[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kd], st[ct], 0, 0, 0);
-            }
-        }
-        // ---- visibility from integers, online softmax (per-lane row statistics)
-        float mx = -1e30f;
-        bool okv[4][4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kl = ct * 16 + lg * 4 + r;
-                const bool ok = NEW ? (krow_[kl] == qr && k0 + kl <= qs) : (k0 + kl < kend);
-                okv[ct][r] = ok;
-                const float s = st[ct][r] * sl2;
-                st[ct][r] = s;
-                if (ok) mx = fmaxf(mx, s);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = exp2f(m_run - m_new);
-        float rs = 0.0f;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = okv[ct][r] ? exp2f(st[ct][r] - m_new) : 0.0f;
-                st[ct][r] = p;
-                rs += p;
-            }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int i = 0; i < DT; ++i) o[i] *= alpha;
-
-        // ---- O^T += V^T P^T.  k-slot (lg, j) of step ks  <->  key k0 + 32 ks + (j < 4 ? lg*4 + j : 16 + lg*4 + j - 4)
-        bf16x8 pb[2];
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pb[ks2][j] = (bf16)st[2 * ks2][j];
-                pb[ks2][4 + j] = (bf16)st[2 * ks2 + 1][j];
-            }
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const char *vrow = vt_ + (dt * 16 + l15) * VSTR + lg * 8;
-#pragma unroll
-            for (int ks2 = 0; ks2 < 2; ++ks2) {
-                const bf16x4 lo = *reinterpret_cast<const bf16x4 *>(vrow + ks2 * 64);
-                const bf16x4 hi = *reinterpret_cast<const bf16x4 *>(vrow + ks2 * 64 + 32);
-                bf16x8 vf;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    vf[j] = lo[j];
-                    vf[4 + j] = hi[j];
-                }
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks2], o[dt], 0, 0, 0);
-            }
-        }
+        // visibility from integers
+        t.step(
+            ks_, vt_, [&](int kl) { return NEW ? (krow_[kl] == qr && k0 + kl <= qs) : (k0 + kl < kend); }, [&](int, float s) { return s * sl2; },
+            [](int, float p) { return p; });
     };
 
     // ---- phase 1: the shared prefix
@@ -164,21 +68,7 @@ __global__ __launch_bounds__(256) void prefix_attn_kernel(const PrefixAttnArgs a
         for (int k0 = w0; k0 < wend; k0 += 64) tile(std::true_type{}, a.kn + h * a.hd, a.ldk, a.vn + h * a.hd, a.ldv, k0, wend);
     }
 
-    // ---- finalize: o[dt][r] = O[q = l15][d = dt*16 + lg*4 + r]
-    if (qs < a.S) {
-        const float inv = l_run > 0.0f ? 1.0f / l_run : 0.0f;
-        bf16 *op = a.o + (int64_t)qs * a.heads * a.hd + h * a.hd;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const int d0 = dt * 16 + lg * 4;
-            if (d0 < a.hd) {
-                bf16x4 w;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) w[r] = (bf16)(o[dt][r] * inv);
-                *reinterpret_cast<bf16x4 *>(op + d0) = w;
-            }
-        }
-    }
+    if (qs < a.S) t.store(a.o + (int64_t)qs * a.heads * a.hd + h * a.hd, a.hd);
 }
 
 bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
