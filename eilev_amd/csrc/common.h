@@ -356,6 +356,21 @@ struct GemmArgs {
 // a row apart: 4.04 -> 3.85 ms / token at batch 32).  A buffer in this layout holds 32 rows whatever M is.  8-element chunks stay contiguous.
 __host__ __device__ static inline int64_t frag32_index(int row, int col) { return (int64_t)(col >> 5) * 1024 + row * 32 + (col & 31); }
 
+// Probe build only: the kernel instance launch_gemm launched last (eilev_debug_gemm reports it; tests/gemm_ref.py names the codes).  Low 16 bits:
+// 1000 gemm_nt_kernel / 2000 gemm_glds_kernel + 10 * tile (1 256 x 256, 2 256 x 128 two stages, 3 256 x 128 one stage, 4 128 x 128,
+// 5 64 x 128) + epi; 3000 + slices: split-K; 4000 + 100 * LN + 10 * instance (0 32 x 32 MFMAs, 1 / 2 the 16 x 16 forms M16K = 1 / 2, 3 A3,
+// 4 fp8 MFMA) + epi: gemm_pp4_kernel; 5000 + epi: gemm_w6_kernel.  Bits above: the launch was cut into row chunks / its fp8 weights expanded.
+// A plain global on purpose: GemmArgs::dbg would move the launch off the product's route.  The product library has neither.
+#ifdef EILEV_PROBES
+extern int g_gemm_form;
+#define GEMM_FORM(code) (g_gemm_form = (g_gemm_form & ~0xffff) | (code))
+#define GEMM_FORM_BIT(bit) (g_gemm_form |= (bit))
+#else
+#define GEMM_FORM(code) ((void)0)
+#define GEMM_FORM_BIT(bit) ((void)0)
+#endif
+enum : int { GEMM_FORM_ROW_CHUNKS = 1 << 16, GEMM_FORM_W8_EXPANDED = 1 << 17 };
+
 int launch_gemm(const GemmArgs &g, int prof_kind, hipStream_t s);
 bool gemm_rows32_takes(const GemmArgs &g);  // would launch_gemm run g on gemm_rows32_kernel (the one kernel of the row-block layout)?
 int launch_pp4_ext(const GemmArgs &g, int grid, hipStream_t s);  // gemm_pp4_ext.hip
@@ -376,7 +391,8 @@ static inline bool pp4_all_lean(const GemmArgs &g) {
 }
 // the launch can write the head-major q|k|v layout (GemmArgs::hm_tok)
 static inline bool hm_takes(const GemmArgs &g) {
-    return g.hm_tok > 0 && g.hm_heads > 0 && g.hm_hd > 64 && g.hm_hd % 8 == 0 && g.N == 3 * g.hm_heads * g.hm_hd && g.ln_rows && g.epi == 0 && !g.resid &&
+    // (hm_tok >= 128: the 128 rows a wave stores cross at most ONE frame boundary — gemm_pp4.h lean_epilogue steps its offsets by a single frame)
+    return g.hm_tok >= 128 && g.hm_heads > 0 && g.hm_hd > 64 && g.hm_hd % 8 == 0 && g.N == 3 * g.hm_heads * g.hm_hd && g.ln_rows && g.epi == 0 && !g.resid &&
            !g.stat_out && !g.scale_cols && pp4_all_lean(g) && g.N % 64 == 0 && g.M % g.hm_tok == 0 && (int64_t)g.M * g.N * 2 < 0xfffffff0ll;
 }
 // gemv.hip: nn.Linear on M <= 8 rows as row dot products with the LayerNorm / flash-decoding merge in its prologue

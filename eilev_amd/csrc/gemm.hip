@@ -28,6 +28,7 @@ int g_eilev_grid_cus = 0;  // 0 = every CU (common.h: eilev_grid_cus); written b
 int g_gemm_debug = 0;  // probe-only switches (tools/gemm_probe.py): GemmArgs::dbg, the DBG_GEMM_* bits of common.h
 extern "C" int eilev_debug_gemm_flags(int f) { g_gemm_debug = f; return 0; }
 extern "C" int eilev_debug_grid_cus(int n) { g_eilev_grid_cus = n; return 0; }
+int g_gemm_form = 0;   // common.h GEMM_FORM: what eilev_debug_gemm (end of this file) reports
 #endif
 #ifdef EILEV_PROBES
 unsigned long long *g_gemm_trace = nullptr;  // probe-only: see GemmArgs::trace
@@ -51,10 +52,10 @@ int launch_pp4(const GemmArgs &g, hipStream_t s) {
     if (g.A8 || g.ln_rows || g.stat_out) return launch_pp4_ext(g, grid, s);  // fp8 MFMA / LayerNorm-folding instances (the other object)
     // 16 x 16 x 32 MFMAs where every tile of the launch is a whole lean tile (gemm_pp4.h: M16)
     if (pp4_all_lean(g) && g.epi != 1) {
-        if (a3_takes(g)) return eilev_launch<gemm_pp4_kernel<0, false, 0, 2, true>>(dim3(grid), dim3(512), smem, s, g);
-        return eilev_with_epi<0, 2>(g.epi, [&](auto e) { return eilev_launch<gemm_pp4_kernel<decltype(e)::value, false, 0, 2>>(dim3(grid), dim3(512), smem, s, g); });
+        if (a3_takes(g)) return GEMM_FORM(4030), eilev_launch<gemm_pp4_kernel<0, false, 0, 2, true>>(dim3(grid), dim3(512), smem, s, g);
+        return eilev_with_epi<0, 2>(g.epi, [&](auto e) { return GEMM_FORM(4020 + decltype(e)::value), eilev_launch<gemm_pp4_kernel<decltype(e)::value, false, 0, 2>>(dim3(grid), dim3(512), smem, s, g); });
     }
-    return eilev_with_epi<0, 1, 2>(g.epi, [&](auto e) { return eilev_launch<gemm_pp4_kernel<decltype(e)::value>>(dim3(grid), dim3(512), smem, s, g); });
+    return eilev_with_epi<0, 1, 2>(g.epi, [&](auto e) { return GEMM_FORM(4000 + decltype(e)::value), eilev_launch<gemm_pp4_kernel<decltype(e)::value>>(dim3(grid), dim3(512), smem, s, g); });
 }
 
 constexpr int64_t kOffsetLimit = 0x7fff0000ll;  // bytes a 32-bit buffer offset (LDS-DMA, buffer loads) reaches, with room for the last tile
@@ -251,6 +252,7 @@ int launch_row_chunks(const GemmArgs &g, int64_t rows_per, int prof_kind, hipStr
         const int rc = launch_gemm(c, prof_kind, s);
         if (rc != EILEV_OK) return rc;
     }
+    GEMM_FORM_BIT(GEMM_FORM_ROW_CHUNKS);
     return EILEV_OK;
 }
 
@@ -297,7 +299,10 @@ int launch_split_k(const GemmArgs &g, hipStream_t s) {
     GemmArgs gs = g;
     gs.k_slice = (nk + slices - 1) / slices;
     slices = (nk + gs.k_slice - 1) / gs.k_slice;
-    EILEV_HIP_CHECK(hipMemsetAsync(g.C, 0, (size_t)g.M * g.ldc * sizeof(float), s));
+    // the M x N output only: with ldc > N the columns between the rows (and the ldc - N words behind the last one) are not this launch's
+    if (g.ldc == g.N) EILEV_HIP_CHECK(hipMemsetAsync(g.C, 0, (size_t)g.M * g.N * sizeof(float), s));
+    else EILEV_HIP_CHECK(hipMemset2DAsync(g.C, (size_t)g.ldc * sizeof(float), 0, (size_t)g.N * sizeof(float), (size_t)g.M, s));
+    GEMM_FORM(3000 + slices);
     return eilev_launch<gemm_glds_kernel<128, 128, 2, 2, 0, 2, 2, 0>>(dim3(tiles, slices), dim3(256), 2 * (128 + 128) * 128, s, gs);
 }
 
@@ -384,6 +389,7 @@ static int launch_gemm_core(const GemmArgs &g_in, int prof_kind, hipStream_t s, 
         if (!w8_streams(g)) {  // expanded, then this launch again on the bf16 copy
             const int rc_x = w8_expand(g, s);
             if (rc_x != EILEV_OK) return rc_x;
+            GEMM_FORM_BIT(GEMM_FORM_W8_EXPANDED);
             GemmArgs e = g_in;
             e.W = g.w8_scratch;
             e.W8 = nullptr;
@@ -397,3 +403,46 @@ static int launch_gemm_core(const GemmArgs &g_in, int prof_kind, hipStream_t s, 
     if (const int64_t rows = chunk_rows(g)) return launch_row_chunks(g_in, rows, prof_kind, s);
     return profiled(ln_fold(g) ? launch_pp4 : launch_wide, g, prof_kind, s);
 }
+
+#ifdef EILEV_PROBES
+// probe / test entry (tests/test_hip_gemm_wide.py): ONE launch_gemm on the caller's buffers.  The struct is GemmArgs field by field as plain
+// pointers and integers, without dbg, trace, trace_tiles and k_slice (the ctypes mirror lives with the tests); struct_bytes must be its
+// size, so a stale mirror is refused instead of run.  *form receives the code of the kernel instance that was launched (common.h
+// GEMM_FORM; 0: none).  eilev_debug_gemm_flags applies as to every launch.
+struct EilevDebugGemmArgs {
+    const void *A; int64_t lda;
+    const void *W; int64_t ldw;
+    const void *bias, *resid; int64_t ldr;
+    void *C; int64_t ldc;
+    int32_t M, N, K, epi, out_f32;
+    float scale;
+    int32_t scale_cols, patch_group, hm_tok, hm_heads, hm_hd, pad0;
+    const float *wscale;
+    const void *W8;
+    void *w8_scratch;
+    const void *A8;
+    const float *ascale, *ln_rows, *ln_csum;
+    float *stat_out; int64_t stat_ld;
+    const void *ln_gamma, *ln_beta;
+    void *ln_out;
+    float ln_eps;
+    int32_t pad1;
+};
+extern "C" int eilev_debug_gemm(const EilevDebugGemmArgs *args, size_t struct_bytes, int *form, void *stream) {
+    if (!args || struct_bytes != sizeof(EilevDebugGemmArgs)) return EILEV_E_BADARG;
+    GemmArgs g = {};
+    g.A = (const bf16 *)args->A; g.lda = args->lda; g.W = (const bf16 *)args->W; g.ldw = args->ldw;
+    g.bias = (const bf16 *)args->bias; g.resid = (const bf16 *)args->resid; g.ldr = args->ldr; g.C = args->C; g.ldc = args->ldc;
+    g.M = args->M; g.N = args->N; g.K = args->K; g.epi = args->epi; g.out_f32 = args->out_f32;
+    g.scale = args->scale; g.scale_cols = args->scale_cols; g.patch_group = args->patch_group;
+    g.hm_tok = args->hm_tok; g.hm_heads = args->hm_heads; g.hm_hd = args->hm_hd;
+    g.wscale = args->wscale; g.W8 = (const uint8_t *)args->W8; g.w8_scratch = (bf16 *)args->w8_scratch;
+    g.A8 = (const uint8_t *)args->A8; g.ascale = args->ascale; g.ln_rows = args->ln_rows; g.ln_csum = args->ln_csum;
+    g.stat_out = args->stat_out; g.stat_ld = args->stat_ld;
+    g.ln_gamma = (const bf16 *)args->ln_gamma; g.ln_beta = (const bf16 *)args->ln_beta; g.ln_out = (bf16 *)args->ln_out; g.ln_eps = args->ln_eps;
+    g_gemm_form = 0;
+    const int rc = launch_gemm(g, -1, (hipStream_t)stream);
+    if (form) *form = g_gemm_form;
+    return rc;
+}
+#endif

@@ -12,7 +12,7 @@ int launch_pp4_ext(const GemmArgs &g, int grid, hipStream_t s) {
         h.A = reinterpret_cast<const bf16 *>(g.A8);
         h.W = reinterpret_cast<const bf16 *>(g.W8);
         h.K = g.K / 2; h.lda = g.lda / 2; h.ldw = g.ldw / 2;
-        return eilev_with_epi<0, 2>(g.epi, [&](auto e) { return eilev_launch<gemm_pp4_kernel<decltype(e)::value, true>>(dim3(grid), dim3(512), smem, s, h); });
+        return eilev_with_epi<0, 2>(g.epi, [&](auto e) { return GEMM_FORM(4040 + decltype(e)::value), eilev_launch<gemm_pp4_kernel<decltype(e)::value, true>>(dim3(grid), dim3(512), smem, s, h); });
     }
     if (g.hm_tok && !hm_takes(g)) return EILEV_E_UNSUPPORTED;  // head-major q|k|v: the 16 x 16 folded-LayerNorm consumer only (common.h)
     // LayerNorm-folding variants: consumer (qkv, fc1 + GELU) / producer (proj, fc2 with the residual)
@@ -21,11 +21,11 @@ int launch_pp4_ext(const GemmArgs &g, int grid, hipStream_t s) {
         return EILEV_E_UNSUPPORTED;
     const bool lean = pp4_all_lean(g);  // the 16 x 16 MFMA instances (gemm_pp4.h M16)
     if (g.stat_out)  // statistics producers (ViT proj / fc2)
-        return lean ? eilev_launch<gemm_pp4_kernel<0, false, 2, 2>>(dim3(grid), dim3(512), smem, s, g)
+        return GEMM_FORM(lean ? 4220 : 4200), lean ? eilev_launch<gemm_pp4_kernel<0, false, 2, 2>>(dim3(grid), dim3(512), smem, s, g)
                     : eilev_launch<gemm_pp4_kernel<0, false, 2>>(dim3(grid), dim3(512), smem, s, g);
     return eilev_with_epi<0, 1>(g.epi, [&](auto e) {  // folded-LayerNorm consumers (ViT qkv / fc1)
         constexpr int EPI = decltype(e)::value;
-        return lean ? eilev_launch<gemm_pp4_kernel<EPI, false, 1, 1>>(dim3(grid), dim3(512), smem, s, g)
+        return GEMM_FORM((lean ? 4110 : 4100) + EPI), lean ? eilev_launch<gemm_pp4_kernel<EPI, false, 1, 1>>(dim3(grid), dim3(512), smem, s, g)
                     : eilev_launch<gemm_pp4_kernel<EPI, false, 1>>(dim3(grid), dim3(512), smem, s, g);
     });
 }

@@ -289,6 +289,8 @@ int launch_tiled_e(const GemmArgs &g, hipStream_t s) {
     constexpr int smem_nt = 2 * (BM + BN) * 128 > epi ? 2 * (BM + BN) * 128 : epi;
     const bool fast = (g.K % BK) == 0 && !(g.dbg & DBG_GEMM_NO_DMA) && (int64_t)g.M * g.lda * 2 < 0x7fff0000ll && (int64_t)g.N * g.ldw * 2 < 0x7fff0000ll;
     const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+    constexpr int shape = BM == 64 ? 5 : BM == 128 ? 4 : BN == 256 ? 1 : NSTAGE == 2 ? 2 : 3;  // common.h GEMM_FORM
+    GEMM_FORM((fast ? 2000 : 1000) + 10 * shape + EPI);
     if (fast) return eilev_launch<gemm_glds_kernel<BM, BN, NWM, NWN, EPI, NSTAGE, MINW, PRIO>>(dim3(tiles), dim3(64 * NWM * NWN), smem, s, g);
     return eilev_launch<gemm_nt_kernel<BM, BN, NWM, NWN, EPI>>(dim3(tiles), dim3(64 * NWM * NWN), smem_nt, s, g);
 }

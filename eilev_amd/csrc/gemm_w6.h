@@ -322,7 +322,7 @@ int launch_w6(const GemmArgs &g, hipStream_t s) {
     const int tiles = ((g.M + 255) / 256) * ((g.N + 127) / 128);
     const int ncu = eilev_grid_cus();
     const int grid = tiles < ncu ? tiles : ncu / 8 * 8;
-    return eilev_with_epi<0, 1, 2>(g.epi, [&](auto e) { return eilev_launch<gemm_w6_kernel<decltype(e)::value>>(dim3(grid), dim3(256), smem, s, g); });
+    return eilev_with_epi<0, 1, 2>(g.epi, [&](auto e) { return GEMM_FORM(5000 + decltype(e)::value), eilev_launch<gemm_w6_kernel<decltype(e)::value>>(dim3(grid), dim3(256), smem, s, g); });
 }
 
 

@@ -145,7 +145,8 @@ def test_c_abi_library_exports_every_declared_symbol():
             assert hasattr(lib, sym), sym
         # round 5: the product library carries no probe switch (they exist in the -DEILEV_PROBES build only)
         for sw in ("eilev_debug_gemm_flags", "eilev_debug_gemm_trace", "eilev_debug_attn_v1", "eilev_debug_attn_ts", "eilev_debug_decode_rows",
-                   "eilev_debug_beam_part", "eilev_debug_fused_patch", "eilev_debug_decode_prefetch", "eilev_debug_reduce_ln_wave", "eilev_debug_attention"):
+                   "eilev_debug_beam_part", "eilev_debug_fused_patch", "eilev_debug_decode_prefetch", "eilev_debug_reduce_ln_wave", "eilev_debug_attention",
+                   "eilev_debug_gemm"):
             assert not hasattr(lib, sw), sw
         # round 6: the dynamic symbol table IS the header — nothing else leaves the library (csrc/exports.map: no C++ launcher, no kernel stub)
         import subprocess
