@@ -714,6 +714,35 @@ def load_prefix() -> C.CDLL:
     return _load_companion(PREFIX_LIB_PATH, PREFIX_ABI_VERSION, declare)
 
 
+# ---- the fp8 KV-cache companion library (include/eilev_kv8.h): the OPT decode step over a cache of e4m3 bytes with one power-of-two scale
+# per head vector.  Like the shared-prefix library it carries its own copy of the core library's code and shares no state with it. ----
+KV8_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_kv8.so")
+KV8_ABI_VERSION = 1
+KV8_RANGE = 256
+KV8_MAX_ROWS = 32
+KV8_EXPORTS = ["eilev_kv8_abi_version", "eilev_kv8_attention", "eilev_kv8_cache_bytes", "eilev_kv8_decode_step", "eilev_kv8_quantize",
+               "eilev_kv8_workspace_bytes"]
+
+
+def kv8_supported(dims) -> bool:
+    """The models the eilev_kv8_* calls take (anything else returns EILEV_E_UNSUPPORTED): head sizes 80 and 128."""
+    return dims is not None and int(dims.t_heads) > 0 and int(dims.t_hidden) // int(dims.t_heads) in (80, 128)
+
+
+def load_kv8() -> C.CDLL:
+    """Load libeilev_hip_kv8.so."""
+    def declare(sig):
+        DP = C.POINTER(Dims)
+        sig("eilev_kv8_cache_bytes", _sz, DP, _i64, _i64)
+        sig("eilev_kv8_workspace_bytes", _sz, DP, _i64)
+        sig("eilev_kv8_quantize", _i32, DP, vp, _i64, _i64, _i64, vp, _i64, vp)
+        sig("eilev_kv8_attention", _i32, vp, _i64, vp, vp, vp, vp, vp, vp, _i64, _i64, _i64, _i64, _i64, _i32, vp, _sz, vp, vp)
+        sig("eilev_kv8_decode_step", _i32, DP, C.POINTER(OptWeights), vp, vp, vp, vp, _i64, _i64, vp, _i64, vp, vp, _i64, _i64, vp, _i64, vp, _sz, vp)
+        return sig("eilev_kv8_abi_version", _i32)
+
+    return _load_companion(KV8_LIB_PATH, KV8_ABI_VERSION, declare)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         names = {-1: "EILEV_E_BADARG", -2: "EILEV_E_UNSUPPORTED", -3: "EILEV_E_WORKSPACE"}

@@ -585,6 +585,14 @@ int launch_attn_cross_shared(const bf16 *q, int64_t ldq, const bf16 *kc, const b
     return EILEV_OK;
 }
 
+// the partials of `nsplit` key ranges per (row, head) (layout of attn_decode_part_bytes) -> out [batch][heads * hd]
+int launch_attn_decode_merge(const float *part, bf16 *out, int batch, int heads, int hd, int nsplit, hipStream_t s) {
+    if (!part || !out || batch <= 0 || heads <= 0 || hd <= 0 || hd > 128 || nsplit <= 0) return EILEV_E_BADARG;
+    hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(heads, batch), dim3(128), 0, s, part, out, heads, hd, nsplit);
+    EILEV_LAUNCH_CHECK();
+    return EILEV_OK;
+}
+
 static int g_beam_part = 1;
 static int g_attn_part32 = 1;  // 1 = by batch size (launch_attn_decode); probe build: 0 = the 256-key split kernel, 2 / 3 = force a form
 #ifdef EILEV_PROBES

@@ -527,6 +527,9 @@ bool attn_decode1_ok(int batch, int cap, int hd);
 int launch_attn_decode1(const DecodeAttnArgs &a, hipStream_t s);
 // ... the same loading scheme over 128-key ranges, partials for gemv1_kernel's merge prologue; *nsplit = the ranges per (row, head)
 int launch_attn_decode_part(const DecodeAttnArgs &a, hipStream_t s, int *nsplit);
+// attn_decode_merge_kernel alone: the partials of `nsplit` key ranges per (row, head) -> out [batch][heads * hd] (kv8.hip leaves its own
+// kernel's partials to it)
+int launch_attn_decode_merge(const float *part, bf16 *out, int batch, int heads, int hd, int nsplit, hipStream_t s);
 // flan-t5 beam search: the cross-attention of `rows` query rows (stride ldq, head size 64) of which every `beams` consecutive ones share one
 // sample's keys / values — planes [rows / beams][heads][cap][hd], keys [0, enc_len), enc_mask (rows / beams, enc_len) or null — read once
 // per (sample, head, 128-key range); partials in `part` (attn_decode_part_bytes(rows, heads, hd, enc_len)), merged into out [rows][heads * hd].

@@ -563,6 +563,23 @@ class HipEngine:
         # not zeroed (10 GB at batch 32): every slot is written (kv_write) before any kernel reads it
         return torch.empty(int(nb), dtype=torch.uint8, device=self.device)
 
+    def _kv8(self, kv_dtype):
+        """The fp8 KV-cache library for kv_dtype "fp8", None for "bf16" / None; no fall-back: a model it does not take is an error."""
+        if kv_dtype in (None, "bf16"):
+            return None
+        if kv_dtype != "fp8":
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', not {kv_dtype!r}")
+        if not abi.kv8_supported(self.dims):
+            raise NotImplementedError("kv_dtype='fp8': the fp8 KV-cache kernels take OPT head sizes 80 and 128")
+        return abi.load_kv8()
+
+    def new_kv8_cache(self, batch, capacity):
+        """An fp8 (e4m3) KV cache with its exponent planes (include/eilev_kv8.h); not zeroed, like new_kv_cache."""
+        nb = abi.load_kv8().eilev_kv8_cache_bytes(C.byref(self.dims), batch, capacity)
+        if not nb:
+            raise RuntimeError("eilev_kv8_cache_bytes refused the shape")
+        return torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+
     def prefill(self, inputs_embeds, attention_mask, kv_cache=None, kv_capacity=None, all_logits=False, last_logits=True, hidden_states=False):
         """OPT prefill.  ``hidden_states=True`` appends the tuple hf returns under ``output_hidden_states`` (every block's input, then the
         output of final_layer_norm; `eilev_opt_prefill_debug`) as a fourth result, (t_layers + 1, B, L, Dt) bf16."""
@@ -758,7 +775,7 @@ class HipEngine:
         return torch.cat(cols, dim=1)
 
     def greedy_decode(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, use_graph=True,
-                      poll_every=8, return_step_logits=False):
+                      poll_every=8, return_step_logits=False, kv_dtype="bf16"):
         """Prefill + KV-cached greedy decode [ref:eilev/model/v2.py:318-322 -> hf generation/utils.py:2783-2941]: _select_decode_device
         with the decode step's own arg-max as the selection.
 
@@ -772,10 +789,10 @@ class HipEngine:
             if return_step_logits:
                 raise NotImplementedError("return_step_logits with more than 32 rows")
             return self._chunked_rows(lambda i, j: self.greedy_decode(inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, use_graph,
-                                                                      poll_every), B, pad_id)
+                                                                      poll_every, kv_dtype=kv_dtype), B, pad_id)
         trace = [] if return_step_logits else None
         ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_list(eos_id), pad_id, ("greedy",), None, None, use_graph,
-                                         poll_every, trace)
+                                         poll_every, trace, kv_dtype)
         return (ids, trace) if return_step_logits else ids
 
     def _pld_buffers(self, text_ids, max_new_tokens, k, vocab):
@@ -859,7 +876,8 @@ class HipEngine:
         return out[:c].reshape(1, c).clone()
 
     def beam_decode(self, inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty=1.0, eos_id=-1, pad_id=1,
-                    early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, use_graph=True, trace=None, rules=None):
+                    early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, use_graph=True, trace=None, rules=None,
+                    kv_dtype="bf16"):
         """Beam search on the HIP path [sample default: num_beams=5, length_penalty=-1; hf generation/utils.py:3208+].
         ``trace``: a list that receives (tokens fed, parent rows, fp32 logits) of every step (tests replay the hypotheses teacher-forced).
         ``rules``: dict(processors=, stopping=, prefix=) for the host loops (eilev_amd/sampling.py, beam.py): hf logits processors / stopping criteria;
@@ -867,7 +885,10 @@ class HipEngine:
         step when `_route_rules` says so (``self.rules_stats`` says which path ran), else as transformers' processors in the host loops.
 
         The prompt is prefilled ONCE per sample; no cache row is ever copied (see below); one HIP decode step on all rows per
-        generated token, captured into a hipGraph and replayed."""
+        generated token, captured into a hipGraph and replayed.
+
+        ``kv_dtype="fp8"`` is served by the two device routes of num_beams == 1 (sample_decode_device, rules_decode_device) only: a call that
+        would take a host loop, or beams, is refused."""
         from .beam import beam_search
 
         d = self.dims
@@ -887,7 +908,8 @@ class HipEngine:
         if sampler is not None and num_beams == 1 and not sampler.get("greedy"):
             sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id, trace)
             if dev_kw is not None:
-                return self.sample_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, **dev_kw)
+                return self.sample_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, kv_dtype=kv_dtype,
+                                                 **dev_kw)
         else:
             # greedy search (num_beams == 1, sampler = dict(greedy=True)) and beam search: the rules run on the device when the route says so and,
             # for beams, when the search takes the fused form; beam-search sampling keeps the host loop
@@ -895,7 +917,10 @@ class HipEngine:
             rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, trace,
                                                             allow_device=(device_loop and advance_ok) or (sampler is not None and num_beams == 1))
             if rules_kw is not None and num_beams == 1:
-                return self.rules_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, **rules_kw)
+                return self.rules_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph,
+                                                kv_dtype=kv_dtype, **rules_kw)
+        if self._kv8(kv_dtype) is not None:
+            raise NotImplementedError("kv_cache_dtype='fp8' is built for the captured device routes only: this call takes beam search or a host loop")
         if R > 32:
             # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are independent in beam search)
             if trace is not None:
@@ -1239,7 +1264,8 @@ class HipEngine:
             setattr(self, stats_name, dict(path="device", steps=n_steps))
         return torch.cat([torch.nn.functional.pad(p, (0, n - p.shape[1]), value=int(pad_id)) for p in parts], dim=0)
 
-    def _select_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace):
+    def _select_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace,
+                              kv_dtype="bf16"):
         """The cached OPT decode: one KV cache of capacity L + max_new, the stream layout, ONE captured step replayed per token (every per-step
         quantity is read from `state` on the device).  ``bind is None`` (greedy_decode): the decode step's own arg-max selects, the first token
         comes from eilev_greedy_select on the prefill's logits.  Else a selection of the caller's runs after the decode step (the draw of
@@ -1252,27 +1278,33 @@ class HipEngine:
         buffers of a new entry.  ``bind(ent) -> (first(logits), step(logits))``: called once per call with the entry's buffers; `first` selects
         from the prefill's logits (state[0] = 0, it finalizes the step itself), `step` from the decode step's (which has already advanced
         state[0]).  ``trace``: a list that receives the prefill's logits and a copy of every eager step's; it turns capture off.  At most 32
-        rows.  Returns int64 (B, n) new tokens."""
+        rows.  Returns int64 (B, n) new tokens.
+
+        ``kv_dtype="fp8"`` (include/eilev_kv8.h): the prompt is prefilled into a bf16 cache of capacity L, quantised into an e4m3 cache of
+        capacity L + max_new (eilev_kv8_quantize), the bf16 cache dropped, and the steps run eilev_kv8_decode_step.  The dtype is part of the
+        graph's key."""
         d = self.dims
         B, L, _ = inputs_embeds.shape
         cap = L + max_new_tokens
         n_dec = max_new_tokens - 1
         if n_dec > 0:
             self.ensure_stream_layout(B)
+        kv8 = self._kv8(kv_dtype)
         graphable = use_graph and n_dec > 1 and trace is None
-        key = tuple(key) + (B, L, cap, max_new_tokens, tuple(eos), int(pad_id))
+        key = tuple(key) + (B, L, cap, max_new_tokens, tuple(eos), int(pad_id), str(kv_dtype))
         ent = self._dec_cache if (graphable and self._dec_cache is not None and self._dec_cache["key"] == key) else None
         if ent is None:
             ent = dict(key=key, graph=None,
                        am=torch.empty((B, L), dtype=torch.int32, device=self.device),
                        n_valid=torch.empty(B, dtype=torch.int32, device=self.device),
-                       kv=self.new_kv_cache(B, cap),
+                       kv=self.new_kv_cache(B, cap) if kv8 is None else self.new_kv8_cache(B, cap),
                        state=torch.zeros(2, dtype=torch.int32, device=self.device),
                        finished=torch.zeros(B, dtype=torch.uint8, device=self.device),
                        tokens=torch.zeros(B, dtype=torch.int64, device=self.device),
                        out=torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device),
                        logits=torch.empty((B, d.vocab), dtype=torch.float32, device=self.device),
-                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1)))
+                       ws=self._workspace("dec", (self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1) if kv8 is None else
+                                                  kv8.eilev_kv8_workspace_bytes(C.byref(d), B))))
             if bind is not None:  # the decode step's own selection goes to buffers that are never read
                 ent.update(argmax_out=torch.zeros((B, max_new_tokens), dtype=torch.int64, device=self.device),
                            argmax_fin=torch.zeros(B, dtype=torch.uint8, device=self.device), **extra(B))
@@ -1292,17 +1324,24 @@ class HipEngine:
         else:
             step_fin, step_eos, step_out = ent["argmax_fin"], -1, ent["argmax_out"]
             first, step = bind(ent)
-        last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
+        if kv8 is None:
+            last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
+        else:  # (the call's peak memory holds one bf16 cache of the prompt: the prefill kernels write bf16)
+            last, _, kv16 = self.prefill(inputs_embeds, am, kv_capacity=L)
+            abi.check(kv8.eilev_kv8_quantize(C.byref(d), _ptr(kv16), B, L, L, _ptr(kv), cap, self._stream()), "eilev_kv8_quantize")
+            del kv16
         self._stamp("prefill_done")
         if trace is not None:
             trace.append(last.clone())
         first(last)
 
+        step_fn, step_name = (self.lib.eilev_opt_decode_step, "eilev_opt_decode_step") if kv8 is None else (kv8.eilev_kv8_decode_step, "eilev_kv8_decode_step")
+
         def one_step():
-            abi.check(self.lib.eilev_opt_decode_step(
+            abi.check(step_fn(
                 C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), B, L, _ptr(kv), cap,
                 _ptr(logits), _ptr(step_fin), step_eos, pad_id, _ptr(step_out), max_new_tokens, _ptr(ws), ws.numel(),
-                self._stream()), "eilev_opt_decode_step")
+                self._stream()), step_name)
             step(logits)
 
         graph = ent["graph"] if graphable else None
@@ -1314,7 +1353,7 @@ class HipEngine:
 
     def sample_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
                              repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None,
-                             no_repeat_ngram_size=0):
+                             no_repeat_ngram_size=0, kv_dtype="bf16"):
         """Multinomial sampling with the draw on the device (include/eilev_sample.h): _select_decode_device with eilev_sample_select after the
         decode step, and eilev_rules_ban in front of it for ``no_repeat_ngram_size`` (hf applies the ban before the warpers).  ``eos_id``: an
         id or up to 8 ids.  ``trace``: a list that receives a copy of every step's logits (use_graph=False; the n-gram ban is already written into them).  ``uniforms``:
@@ -1335,7 +1374,7 @@ class HipEngine:
                 raise ValueError("trace: at most 32 decode rows")
             return self._chunked_rows(lambda i, j: self.sample_decode_device(
                 inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, temperature, top_k, top_p, repetition_penalty, min_new_tokens,
-                None, use_graph, poll_every, None, uni_all[:, i:j], ngram), B, pad_id, "sample_stats")
+                None, use_graph, poll_every, None, uni_all[:, i:j], ngram, kv_dtype), B, pad_id, "sample_stats")
         rl, ban_params = self._rules_setup(d.vocab, max_new_tokens, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id) if ngram else (None, None)
 
         def extra(rows):
@@ -1357,12 +1396,13 @@ class HipEngine:
             return select(ban_params(0, 0) if ngram else None, params(0, 1)), select(ban_params(-1, 0) if ngram else None, params(-1, 0))
 
         key = ("sample", float(temperature), int(top_k or 0), float(top_p), float(repetition_penalty), int(min_new_tokens), ngram)
-        ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace)
+        ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace,
+                                         kv_dtype)
         self.sample_stats = dict(path="device", steps=int(ids.shape[1]))
         return ids
 
     def rules_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                            min_new_tokens=0, use_graph=True, poll_every=8, trace=None):
+                            min_new_tokens=0, use_graph=True, poll_every=8, trace=None, kv_dtype="bf16"):
         """Greedy search with logits rules on the device (include/eilev_rules.h): _select_decode_device with eilev_rules_select — repetition
         penalty, n-gram ban, minimum length, up to 8 EOS ids, then the arg-max — after the decode step.  ``trace``: a list that receives a
         copy of every step's logits (use_graph=False).  Returns int64 (B, n) new tokens."""
@@ -1380,8 +1420,8 @@ class HipEngine:
             if trace is not None:
                 raise ValueError("trace: at most 32 decode rows")
             return self._chunked_rows(lambda i, j: self.rules_decode_device(
-                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, repetition_penalty, ngram, min_new_tokens, use_graph, poll_every),
-                B, pad_id, "rules_stats")
+                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, repetition_penalty, ngram, min_new_tokens, use_graph, poll_every,
+                kv_dtype=kv_dtype), B, pad_id, "rules_stats")
 
         def bind(ent):
             def select(p):
@@ -1390,7 +1430,7 @@ class HipEngine:
 
         key = ("rules", float(repetition_penalty), ngram, int(min_new_tokens))
         ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, lambda rows: {}, bind, use_graph, poll_every,
-                                         trace)
+                                         trace, kv_dtype)
         self.rules_stats = dict(path="device", steps=int(ids.shape[1]))
         return ids
 

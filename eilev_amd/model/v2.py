@@ -14,6 +14,8 @@ beam search apply them on the device in the decode step, for OPT and for flan-t5
 copying or replicating a cache: include/eilev_t5beam.h); beam-search sampling and user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
 ``encode_context`` prefills a leading part that many calls share — the in-context examples — once; ``generate(context=...)`` and
 ``classify(share_prompt_cache=True)`` then run their rows over that one cached prefix (include/eilev_prefix.h; plain greedy search on OPT).
+``generate(kv_cache_dtype="fp8")`` keeps the OPT decode step's KV cache in e4m3 bytes with power-of-two scales (include/eilev_kv8.h; greedy
+search, sampling and the logits rules on their device routes).
 ``output_hidden_states`` / ``output_attentions`` inside the full model's ``forward`` are served from slow paths for the vision wrapper,
 the Q-Former (self- and cross-attention weights), the OPT language model and the T5 stacks (hidden states; self- and cross-attention weights).  ``decoder_attention_mask`` with padding is honoured on the evaluation route (the first target position of a row must stay visible).
 """
@@ -509,6 +511,11 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             self._preprocess_accelerate()
         kw = dict(generate_kwargs)
         context = kw.pop("context", None)  # a VideoContext: input_ids / pixel_values describe only what follows it
+        # "fp8": the decode steps keep their KV cache in e4m3 bytes with power-of-two scales (include/eilev_kv8.h); None / "bf16": the default
+        kv_dtype = kw.pop("kv_cache_dtype", None)
+        if kv_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype must be None, 'bf16' or 'fp8', not {kv_dtype!r}")
+        kv_dtype = kv_dtype or "bf16"
         num_beams = kw.pop("num_beams", 1)
         do_sample = kw.pop("do_sample", False)
         length_penalty = kw.pop("length_penalty", 1.0)  # only affects beam search
@@ -634,6 +641,27 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             if context.P + input_ids.shape[1] + int(max_new) > limit:
                 raise ValueError(f"context ({context.P}) + input_ids ({input_ids.shape[1]}) + max_new_tokens ({int(max_new)}) exceed "
                                  f"max_position_embeddings ({limit})")
+        if kv_dtype == "fp8":  # served by the three captured device routes of the OPT decode step; everything is checked here, before any encode
+            from .. import abi as _abi
+
+            t_cfg = self.config.text_config
+            heads = int(getattr(t_cfg, "num_attention_heads", 0) or 0)
+            head_ok = not self._is_t5 and heads > 0 and int(t_cfg.hidden_size) // heads in (80, 128)
+            eng0 = self._hip[1] if self._hip is not None else None  # (an engine that exists: its route switches; a new one has both on)
+            with_rules0 = len(eos_ids) > 1 or min_new > 0 or rules is not None
+            combo = [n for n, on in (("the flan-t5 language model", self._is_t5), ("num_beams > 1", num_beams > 1), ("context=", context is not None),
+                                     ("prompt_lookup_num_tokens", lookup is not None),
+                                     ("a head size other than 80 / 128", not self._is_t5 and not head_ok),
+                                     ("logits_processor (a host loop)", bool(user_procs)),
+                                     ("stopping criteria / max_time (a host loop)", len(crit) > 0),
+                                     ("more than 8 EOS ids (a host loop)", len(eos_ids) > min(_abi.SAMPLE_MAX_EOS, _abi.RULES_MAX_EOS)),
+                                     ("a vocabulary the device selection does not take (a host loop)",
+                                      (sampler is not None or with_rules0) and not (_abi.sample_supported(t_cfg.vocab_size) and _abi.rules_supported(t_cfg.vocab_size))),
+                                     ("device_sampling off (a host loop)", sampler is not None and not getattr(eng0, "device_sampling", True)),
+                                     ("device_rules off (a host loop)", sampler is None and with_rules0 and not getattr(eng0, "device_rules", True))) if on]
+            if combo:
+                raise NotImplementedError(f"generate(kv_cache_dtype='fp8') with {', '.join(combo)} is not built on the HIP path (greedy search, sampling "
+                                          "and the logits rules of the captured OPT decode step are)")
         if want_dict and not (want_scores or want_logits):  # sequences only: any decoding mode, wrapped like hf wraps it
             from transformers.generation.utils import GenerateDecoderOnlyOutput, GenerateEncoderDecoderOutput
 
@@ -677,7 +705,8 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             from transformers.generation.utils import GenerateDecoderOnlyOutput
 
             if plain_greedy and not self._is_t5 and (want_scores or want_logits):
-                ids, steps = eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad), use_graph=False, return_step_logits=True)
+                ids, steps = eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad), use_graph=False, return_step_logits=True,
+                                               kv_dtype=kv_dtype)
                 steps = tuple(st_[:, : self.config.text_config.vocab_size].float() for st_ in steps[: ids.shape[1]])
                 return GenerateDecoderOnlyOutput(sequences=ids, scores=steps if want_scores else None, logits=steps if want_logits else None)
             raise AssertionError("unreachable: the sequences-only form returned before the encode")
@@ -702,8 +731,8 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         if sampler is not None or with_rules:
             rule = dict(sampler) if sampler is not None else dict(greedy=True)
             return eng.beam_decode(emb, attention_mask, int(max_new), 1, eos_id=eos_ids if with_rules else eos1, pad_id=int(pad),
-                                   sampler=dict(rule, min_new_tokens=min_new), rules=rules)
-        return eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad))
+                                   sampler=dict(rule, min_new_tokens=min_new), rules=rules, kv_dtype=kv_dtype)
+        return eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad), kv_dtype=kv_dtype)
 
     @torch.no_grad()
     def encode_context(self, input_ids, pixel_values=None, video_input_mask=None) -> VideoContext:
