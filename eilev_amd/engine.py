@@ -10,7 +10,8 @@ import ctypes as C
 
 import torch
 
-from . import abi
+from . import abi, route
+from .sampling import eos_list
 
 
 def _ptr(t):
@@ -660,8 +661,6 @@ class HipEngine:
         slots [0, n) are to it n tokens already generated) and eilev_greedy_select on a second counter.  The most recent graph is kept with
         its buffers and reused by a call of the same shape on the same context.  ``trace``: a list that receives the extend's logits and every
         eager step's; it turns capture off.  Returns int64 (R, steps) new tokens."""
-        from .sampling import eos_list
-
         d = self.dims
         R, n, _ = new_embeds.shape
         if max_new_tokens <= 0:
@@ -780,8 +779,6 @@ class HipEngine:
         with the decode step's own arg-max as the selection.
 
         Returns int64 (B, n_steps) of NEW tokens only (OPT path)."""
-        from .sampling import eos_list
-
         B = inputs_embeds.shape[0]
         if max_new_tokens <= 0:
             return torch.empty((B, 0), dtype=torch.int64, device=self.device)
@@ -818,6 +815,23 @@ class HipEngine:
                                      self._stream()), "eilev_pld_step")
         return b["status"].tolist()  # the one read-back of the step
 
+    def _lookup_head(self, B, num_tokens, ngram, max_new_tokens):
+        """What the two prompt-lookup loops begin with: batch 1, draft length and n-gram size in range, ``pld_stats`` reset -> (k, n_new)."""
+        if B != 1:
+            raise ValueError("assisted generate is only supported for batch_size = 1")
+        k, n_new = int(num_tokens), int(max_new_tokens)
+        if not 1 <= k <= abi.PLD_MAX_K or int(ngram) < 1:
+            raise ValueError(f"prompt_lookup_num_tokens must be in 1..{abi.PLD_MAX_K} and max_matching_ngram_size >= 1")
+        self.pld_stats = dict(verify=0, single=0, accepted=0)
+        return k, n_new
+
+    def _lookup_tail(self, status, verify, single, commit, out):
+        """... and end with: eilev_amd/pld.py lookup_loop from the first status block; the committed ids (1, c), a view of ``out``."""
+        from .pld import lookup_loop
+
+        c = lookup_loop(status, verify, single, commit, self.pld_stats)
+        return out[:c].reshape(1, c)
+
     def greedy_lookup_decode(self, inputs_embeds, attention_mask, text_ids, max_new_tokens, num_tokens=10, ngram=2, eos_id=-1, pad_id=1, trace=None):
         """Greedy decoding with prompt-lookup drafts [hf generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=n), batch 1]:
         returns the ids of greedy_decode, int64 (1, n) of NEW tokens.  ``text_ids``: the row's visible text ids (no left padding, no
@@ -825,17 +839,9 @@ class HipEngine:
         ids, or < 0.  The prompt is prefilled once; each step verifies [last, d1 .. dm] with eilev_opt_extend, or runs the plain
         decode step when there is no draft; libeilev_hip_pld.so commits and drafts.  No hipGraph: the shapes change per step.
         Counters of the call: ``self.pld_stats``.  ``trace``: a list that receives a copy of the logits every commit read (tests)."""
-        from .pld import lookup_loop
-        from .sampling import eos_list
-
         d = self.dims
         B, L, _ = inputs_embeds.shape
-        if B != 1:
-            raise ValueError("assisted generate is only supported for batch_size = 1")
-        k, n_new = int(num_tokens), int(max_new_tokens)
-        if not 1 <= k <= abi.PLD_MAX_K or int(ngram) < 1:
-            raise ValueError(f"prompt_lookup_num_tokens must be in 1..{abi.PLD_MAX_K} and max_matching_ngram_size >= 1")
-        self.pld_stats = dict(verify=0, single=0, accepted=0)
+        k, n_new = self._lookup_head(B, num_tokens, ngram, max_new_tokens)
         if n_new <= 0:
             return torch.empty((1, 0), dtype=torch.int64, device=self.device)
         eos = eos_list(eos_id)
@@ -872,8 +878,7 @@ class HipEngine:
                 trace.append(lg[:rows].clone())
             return self._pld_commit(pld, params, b, lg, rows, d.vocab)
 
-        c = lookup_loop(commit(last, 1), verify, single, commit, self.pld_stats)  # the first id: the prefill's last logits
-        return out[:c].reshape(1, c).clone()
+        return self._lookup_tail(commit(last, 1), verify, single, commit, out).clone()  # the first id: the prefill's last logits
 
     def beam_decode(self, inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty=1.0, eos_id=-1, pad_id=1,
                     early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, use_graph=True, trace=None, rules=None,
@@ -882,56 +887,37 @@ class HipEngine:
         ``trace``: a list that receives (tokens fed, parent rows, fp32 logits) of every step (tests replay the hypotheses teacher-forced).
         ``rules``: dict(processors=, stopping=, prefix=) for the host loops (eilev_amd/sampling.py, beam.py): hf logits processors / stopping criteria;
         and the numbers repetition_penalty= / no_repeat_ngram_size=, which — like min_new_tokens and several EOS ids — run on the device in the
-        step when `_route_rules` says so (``self.rules_stats`` says which path ran), else as transformers' processors in the host loops.
+        step when the plan (eilev_amd/route.py plan_decode) says so (``self.rules_stats`` says which path ran), else as transformers' processors in the host loops.
 
         The prompt is prefilled ONCE per sample; no cache row is ever copied (see below); one HIP decode step on all rows per
         generated token, captured into a hipGraph and replayed.
 
         ``kv_dtype="fp8"`` is served by the two device routes of num_beams == 1 (sample_decode_device, rules_decode_device) only: a call that
         would take a host loop, or beams, is refused."""
-        from .beam import beam_search
-
         d = self.dims
         B, L, _ = inputs_embeds.shape
         R = B * num_beams
         if num_beams > 32:
             raise NotImplementedError("num_beams > 32")
-        from .sampling import eos_list
-
-        # The fused form of the device loop, stated once as the two facts used below: the per-row top-k kernel takes this call (its vocabulary,
-        # `keep` candidates per row), and so does the kernel that advances the hypotheses
-        eos_l = eos_list(eos_id)
-        gen_cap = max(1, max_new_tokens)
-        topk_ok, advance_ok = self._beam_kernels_ok(d.vocab, num_beams, eos_l, gen_cap)
-        device_loop = sampler is None and num_beams > 1 and self.beam_device_loop
-        rules_kw, with_rules, rules_in = None, False, rules
-        if sampler is not None and num_beams == 1 and not sampler.get("greedy"):
-            sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id, trace)
-            if dev_kw is not None:
-                return self.sample_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, kv_dtype=kv_dtype,
-                                                 **dev_kw)
-        else:
-            # greedy search (num_beams == 1, sampler = dict(greedy=True)) and beam search: the rules run on the device when the route says so and,
-            # for beams, when the search takes the fused form; beam-search sampling keeps the host loop
-            min_new = int(min_new_tokens) if sampler is None else int(sampler.get("min_new_tokens", 0) or 0)
-            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, trace,
-                                                            allow_device=(device_loop and advance_ok) or (sampler is not None and num_beams == 1))
-            if rules_kw is not None and num_beams == 1:
-                return self.rules_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph,
-                                                kv_dtype=kv_dtype, **rules_kw)
+        plan = route.plan_decode(route.Caps.of(self), num_beams, sampler, rules, eos_id, min_new_tokens, max_new_tokens, trace is not None, kv_dtype,
+                                 in_search_loop=True)
+        device = dict(sample_device=self.sample_decode_device, rules_device=self.rules_decode_device).get(plan.route)
+        if device is not None:
+            return device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph, kv_dtype=kv_dtype,
+                          **plan.dev_kw)
         if self._kv8(kv_dtype) is not None:
             raise NotImplementedError("kv_cache_dtype='fp8' is built for the captured device routes only: this call takes beam search or a host loop")
-        if R > 32:
-            # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are independent in beam search)
+        if B > plan.chunk:
+            # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are independent in beam
+            # search); every part is planned again from the caller's arguments
             if trace is not None:
                 raise ValueError("trace: at most 32 decode rows")
-            if rules and rules.get("prefix") is not None:
+            if plan.rules and plan.rules.get("prefix") is not None:
                 raise NotImplementedError("prefix ids with more than 32 decode rows")
-            if rules_kw is not None or with_rules:  # (every part is routed again: it gets the caller's rules, numbers included)
-                rules = rules_in
             return self._chunked_rows(lambda i, j: self.beam_decode(
                 inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, num_beams, length_penalty, eos_id, pad_id, early_stopping, num_return_sequences,
-                sampler, min_new_tokens, use_graph, None, rules), B, pad_id, per=max(1, 32 // num_beams))
+                sampler, min_new_tokens, use_graph, None, rules), B, pad_id, per=plan.chunk)
+        gen_cap = max(1, max_new_tokens)
         am = attention_mask.to(self.device, torch.int32).contiguous()
         # The KV cache is never moved (round 3; before: a torch index_select of the whole cache per step, 1.6 GB at 5 beams x L = 960):
         # the prompt's keys / values stay in the prefill cache (one row per SAMPLE, capacity L), generated tokens go to a generation
@@ -975,30 +961,15 @@ class HipEngine:
                 trace.append((next_tokens.clone(), beam_src.clone(), logits.clone()))
             return logits
 
-        if device_loop and (rules_kw is not None or (not rules and int(min_new_tokens) == 0)) and trace is None:
+        if plan.route == "beam_device":
             # (r4) plain beam search — the sample script's call: selection, ancestor-table update and the decode step as ONE captured graph per
             # generated token, nothing indexed by the step on the host (eilev_amd/beam.py::beam_search_device)
             out = self._beam_device_loop(launch, last, B, num_beams, max_new_tokens, d.vocab, state, tokens, anc, logits, length_penalty, eos_id, pad_id,
-                                         early_stopping, num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok)
+                                         early_stopping, num_return_sequences, use_graph, plan.dev_kw, plan.topk_ok, plan.advance_ok)
             self._decode_warm = True
             return out
-        if sampler is not None and num_beams == 1:  # multinomial sampling: eilev_amd/sampling.py on the same decode step
-            from .sampling import sample_loop
-
-            ids = sample_loop(step, last, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
-        else:
-            ids = beam_search(step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping,
-                              num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
-        self._host_stats(ids, sampler, num_beams, with_rules)
-        return ids
-
-    def _beam_kernels_ok(self, vocab, num_beams, eos_l, gen_cap):
-        """(topk_ok, advance_ok) of a beam search call: the per-row top-k kernel takes it (its vocabulary, `keep` candidates per row), and so
-        does the kernel that advances the hypotheses."""
-        keep = max(2, 1 + len(eos_l)) * num_beams
-        topk_ok = self.beam_topk_kernel and vocab <= 65536 and vocab % 4 == 0 and keep <= 64
-        advance_ok = topk_ok and self.beam_advance_kernel and num_beams * keep <= 2048 and gen_cap * num_beams <= 2048 and len(eos_l) <= 8
-        return topk_ok, advance_ok
+        return self._host_loop(plan, step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping, num_return_sequences,
+                               min_new_tokens)
 
     def _beam_device_loop(self, launch, first, B, num_beams, max_new_tokens, vocab, state, tokens, anc, logits, length_penalty, eos_id, pad_id,
                           early_stopping, num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok, prefix_id=-1):
@@ -1007,7 +978,6 @@ class HipEngine:
         and increments state[0].  ``first``: the (B, vocab) logits in front of the first selection.  ``prefix_id``: the id the rules see in front
         of a hypothesis (flan-t5's decoder start token)."""
         from .beam import beam_search_device
-        from .sampling import eos_list
 
         eos_l = eos_list(eos_id)
         keep = max(2, 1 + len(eos_l)) * num_beams
@@ -1070,14 +1040,24 @@ class HipEngine:
             self.rules_stats = dict(path="device", steps=int(out.shape[1]))
         return out
 
-    def _host_stats(self, ids, sampler, num_beams, with_rules):
-        """What a call that ran one of the host loops (sample_loop, beam_search) records: sample_stats when it drew, rules_stats when it
-        carried rules (beam-search sampling records the former only)."""
+    def _host_loop(self, plan, step, first, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping, num_return_sequences,
+                   min_new_tokens):
+        """The host loop of a plan (eilev_amd/sampling.py sample_loop, beam.py beam_search) over the decode step ``step``, and what such a
+        call records: sample_stats when it drew, rules_stats when it carried rules (beam-search sampling records the former only)."""
+        from . import beam, sampling
+
+        rules = plan.rules or {}
+        if plan.loop == "sample_loop":  # multinomial sampling, and greedy search with host rules
+            ids = sampling.sample_loop(step, first, max_new_tokens, eos_id, pad_id, **plan.sampler, **{k: v for k, v in rules.items() if k != "fill_id"})
+        else:
+            ids = beam.beam_search(step, first, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping, num_return_sequences,
+                                   sampler=plan.sampler, min_new_tokens=min_new_tokens, **rules)
         rec = dict(path="host", steps=int(ids.shape[1]))
-        if sampler is not None:
+        if plan.sampler is not None:
             self.sample_stats = rec
-        if with_rules and (sampler is None or num_beams == 1):
+        if plan.with_rules and (plan.sampler is None or num_beams == 1):
             self.rules_stats = dict(rec)
+        return ids
 
     def sample_decode(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
                       generator=None, repetition_penalty=1.0, min_new_tokens=0):
@@ -1086,73 +1066,6 @@ class HipEngine:
         return self.beam_decode(inputs_embeds, attention_mask, max_new_tokens, 1, eos_id=eos_id, pad_id=pad_id,
                                 sampler=dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator,
                                              repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens))
-
-    def _route_sampling(self, sampler, rules, vocab, eos_id, trace=None):
-        """Where a `sampler is not None and num_beams == 1` call runs.  Returns (sampler, rules, dev_kw): dev_kw is the keyword set of
-        sample_decode_device / t5_sample_device when the device path takes the call, else None with (sampler, rules) in the form the host
-        loop (eilev_amd/sampling.py sample_loop) takes — a numeric repetition_penalty / no_repeat_ngram_size becomes transformers' processor
-        again."""
-        from .sampling import eos_list
-
-        sampler = dict(sampler)
-        pen, ngram, host_only, to_host = HipEngine._rule_numbers(sampler, rules)
-        if (self.device_sampling and not host_only and trace is None and not sampler.get("greedy") and
-                len(eos_list(eos_id)) <= abi.SAMPLE_MAX_EOS and abi.sample_supported(vocab) and (not ngram or abi.rules_supported(vocab))):
-            dev_kw = dict(temperature=sampler.get("temperature", 1.0), top_k=sampler.get("top_k", 50), top_p=sampler.get("top_p", 1.0),
-                          repetition_penalty=pen, min_new_tokens=sampler.get("min_new_tokens", 0), generator=sampler.get("generator"))
-            if ngram:
-                dev_kw["no_repeat_ngram_size"] = ngram
-            return sampler, rules, dev_kw
-        return sampler, to_host(rules), None
-
-    @staticmethod
-    def _rule_numbers(carrier, rules):
-        """Head and tail of the two routes.  Pops the numbers repetition_penalty / no_repeat_ngram_size from ``carrier`` (the route's own copy
-        of the dict that carries them).  Returns (pen, ngram, host_only, to_host): host_only — ``rules`` holds a user processor or a stopping
-        criterion; to_host(rules) — the rules with the numbers as transformers' processors again, the form the host loops take."""
-        pen = float(carrier.pop("repetition_penalty", None) or 1.0)
-        ngram = int(carrier.pop("no_repeat_ngram_size", None) or 0)
-        host_only = bool(rules) and (rules.get("processors") is not None or rules.get("stopping") is not None)
-
-        def to_host(rules):
-            if pen != 1.0 or ngram:
-                rules = dict(rules or {})
-                rules["processors"] = HipEngine._host_processors(pen, ngram, rules.get("processors"))
-                rules.setdefault("stopping", None)
-            return rules
-
-        return pen, ngram, host_only, to_host
-
-    @staticmethod
-    def _host_processors(pen, ngram, more=None):
-        """The numeric rules as transformers' own processors, in hf's order, in front of the caller's."""
-        from transformers import LogitsProcessorList, NoRepeatNGramLogitsProcessor, RepetitionPenaltyLogitsProcessor
-
-        lst = LogitsProcessorList()
-        if pen != 1.0:
-            lst.append(RepetitionPenaltyLogitsProcessor(penalty=pen))
-        if ngram:
-            lst.append(NoRepeatNGramLogitsProcessor(ngram))
-        lst.extend(list(more or []))
-        return lst
-
-    def _route_rules(self, rules, vocab, eos_id, min_new_tokens=0, trace=None, allow_device=True):
-        """Where a greedy or beam search call with rules runs.  ``rules`` may carry the numbers ``repetition_penalty`` and
-        ``no_repeat_ngram_size`` beside processors= / stopping= / prefix= / fill_id=.  Returns (dev_kw, rules, with_rules): dev_kw is the
-        keyword set of the device path (rules_decode_device, t5_rules_device, the eilev_rules_topk_logprob closure of beam_decode) when it
-        takes the call — no user processor, no stopping criterion, no trace, at most 8 EOS ids, a vocabulary the library takes — else None
-        with ``rules`` in the form the host loops take: the numbers as transformers' processors again.  with_rules: the call carries any
-        rule at all (a plain call is not routed and leaves rules_stats alone)."""
-        from .sampling import eos_list
-
-        rules = dict(rules or {})
-        pen, ngram, host_only, to_host = HipEngine._rule_numbers(rules, rules)
-        n_eos = len(eos_list(eos_id))
-        with_rules = pen != 1.0 or ngram > 0 or int(min_new_tokens) > 0 or n_eos > 1 or host_only
-        if (with_rules and allow_device and self.device_rules and not host_only and trace is None and
-                n_eos <= abi.RULES_MAX_EOS and abi.rules_supported(vocab)):
-            return dict(repetition_penalty=pen, no_repeat_ngram_size=ngram, min_new_tokens=int(min_new_tokens)), (rules or None), True
-        return None, (to_host(rules) or None), with_rules
 
     def _sample_setup(self, R, vocab, max_new_tokens, generator, uniforms, **spec):
         """The sampling library, the uniforms of a whole call — (max_new, R), drawn ONCE on the generator's device — and a function that makes
@@ -1171,11 +1084,6 @@ class HipEngine:
 
         return smp, uniforms, params
 
-    def _sample_select(self, smp, params, logits, R, vocab, uni, state, finished, tokens, out, scratch, warped=None):
-        abi.check(smp.eilev_sample_select(C.byref(params), _ptr(logits), R, vocab, _ptr(uni), _ptr(state), _ptr(finished), _ptr(tokens), _ptr(out),
-                                          _ptr(warped) if warped is not None else None, _ptr(scratch) if scratch.numel() else None, scratch.numel(),
-                                          self._stream()), "eilev_sample_select")
-
     def _rules_setup(self, vocab, max_new_tokens, **spec):
         """The rules library and a function that makes the parameter block of one of its calls."""
         rl = abi.load_rules()
@@ -1186,13 +1094,6 @@ class HipEngine:
             return abi.rules_params(max_new=max_new_tokens, step_offset=step_offset, finalize=finalize, **spec)
 
         return rl, params
-
-    def _rules_select(self, rl, params, logits, R, vocab, state, finished, tokens, out):
-        abi.check(rl.eilev_rules_select(C.byref(params), _ptr(logits), R, vocab, _ptr(state), _ptr(finished), _ptr(tokens), _ptr(out), None, None, 0,
-                                        self._stream()), "eilev_rules_select")
-
-    def _rules_ban(self, rl, params, logits, R, vocab, state, out):
-        abi.check(rl.eilev_rules_ban(C.byref(params), _ptr(logits), R, vocab, _ptr(state), _ptr(out), self._stream()), "eilev_rules_ban")
 
     def _stamp(self, name):
         """Optional phase stamps for bench.py (events on the launch stream, no sync)."""
@@ -1275,9 +1176,9 @@ class HipEngine:
         The captured step only depends on buffer ADDRESSES and on ``key`` — the kind of the call and what its selection depends on (the
         parameter block is passed by value) — plus (B, L, cap, eos, pad): the most recent graph is kept with its buffers in ONE slot and reused
         by calls of the same key (a call of another kind replaces it, so one KV cache is kept at a time).  ``extra(B)``: the selection's own
-        buffers of a new entry.  ``bind(ent) -> (first(logits), step(logits))``: called once per call with the entry's buffers; `first` selects
-        from the prefill's logits (state[0] = 0, it finalizes the step itself), `step` from the decode step's (which has already advanced
-        state[0]).  ``trace``: a list that receives the prefill's logits and a copy of every eager step's; it turns capture off.  At most 32
+        buffers of a new entry.  ``bind(ent, step_offset, finalize) -> select(logits)``: the selection's closure over the entry's buffers, asked
+        for twice per call; (0, 1) selects from the prefill's logits (state[0] = 0, it finalizes the step itself), (-1, 0) from the decode
+        step's (which has already advanced state[0]).  ``trace``: a list that receives the prefill's logits and a copy of every eager step's; it turns capture off.  At most 32
         rows.  Returns int64 (B, n) new tokens.
 
         ``kv_dtype="fp8"`` (include/eilev_kv8.h): the prompt is prefilled into a bf16 cache of capacity L, quantised into an e4m3 cache of
@@ -1323,7 +1224,7 @@ class HipEngine:
             first, step = (lambda lg: self._greedy_select(lg, B, d.vocab, state, finished, step_eos, pad_id, tokens, out)), (lambda lg: None)
         else:
             step_fin, step_eos, step_out = ent["argmax_fin"], -1, ent["argmax_out"]
-            first, step = bind(ent)
+            first, step = bind(ent, 0, 1), bind(ent, -1, 0)  # (the decode step has already advanced state[0]: step_offset -1, no finalize)
         if kv8 is None:
             last, _, _ = self.prefill(inputs_embeds, am, kv_cache=kv, kv_capacity=cap)
         else:  # (the call's peak memory holds one bf16 cache of the prompt: the prefill kernels write bf16)
@@ -1351,92 +1252,103 @@ class HipEngine:
         done_steps = self._run_steps(n_dec, one_step, graph, state, eos, poll_every, trace, logits)
         return self._trim_at_eos(out, 1 + done_steps, eos)
 
+    def _sampling_selection(self, rows, vocab, max_new, prefix_id, eos, pad_id, generator=None, uniforms=None, no_repeat_ngram_size=0, **warp):
+        """Sampling (+ n-gram ban) as a selection (key, extra, bind, uniforms) of the two decode loops: eilev_sample_select after the decode
+        step, eilev_rules_ban in front of it (hf applies the ban before the warpers).  ``extra(rows)``: the selection's own buffers;
+        ``bind(bufs, step_offset, finalize)``: its closure over the loop's buffers and those; ``uniforms``: the whole call's, (max_new, rows)."""
+        ngram, min_new = int(no_repeat_ngram_size or 0), warp.pop("min_new_tokens", 0)
+        smp, uni_all, params = self._sample_setup(rows, vocab, max_new, generator, uniforms, eos_ids=eos, pad_id=pad_id, prefix_id=prefix_id,
+                                                  min_new=min_new, **warp)
+        rl, ban_params = self._rules_setup(vocab, max_new, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id, prefix_id=prefix_id) if ngram else (None, None)
+
+        def extra(rows):
+            return dict(uni=torch.empty((max_new, rows), dtype=torch.float32, device=self.device),
+                        scratch=torch.empty(int(smp.eilev_sample_scratch_bytes(rows, vocab)), dtype=torch.uint8, device=self.device))
+
+        def bind(b, step_offset, finalize):
+            p_ban, p_draw = (ban_params(step_offset, 0) if ngram else None), params(step_offset, finalize)
+            if finalize:  # (asked once per call: the call's uniforms go into the loop's buffer)
+                b["uni"].copy_(uni_all)
+
+            state, out, scratch = b["state"], b["out"], b["scratch"]
+
+            def select(lg):
+                if ngram:
+                    abi.check(rl.eilev_rules_ban(C.byref(p_ban), _ptr(lg), rows, vocab, _ptr(state), _ptr(out), self._stream()), "eilev_rules_ban")
+                abi.check(smp.eilev_sample_select(C.byref(p_draw), _ptr(lg), rows, vocab, _ptr(b["uni"]), _ptr(state), _ptr(b["finished"]), _ptr(b["tokens"]),
+                                                  _ptr(out), None, _ptr(scratch) if scratch.numel() else None, scratch.numel(), self._stream()),
+                          "eilev_sample_select")
+            return select
+
+        key = ("sample", float(warp["temperature"]), int(warp["top_k"] or 0), float(warp["top_p"]), float(warp["repetition_penalty"]), int(min_new), ngram)
+        return key, extra, bind, uni_all
+
+    def _rules_selection(self, rows, vocab, max_new, prefix_id, eos, pad_id, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+        """The logits rules as a selection of the two decode loops (see _sampling_selection): eilev_rules_select — repetition penalty, n-gram
+        ban, minimum length, up to 8 EOS ids, then the arg-max — after the decode step."""
+        ngram = int(no_repeat_ngram_size or 0)
+        rl, params = self._rules_setup(vocab, max_new, repetition_penalty=repetition_penalty, no_repeat_ngram=ngram, min_new=min_new_tokens, eos_ids=eos,
+                                       pad_id=pad_id, prefix_id=prefix_id)
+
+        def bind(b, step_offset, finalize):
+            p = params(step_offset, finalize)
+            return lambda lg: abi.check(rl.eilev_rules_select(C.byref(p), _ptr(lg), rows, vocab, _ptr(b["state"]), _ptr(b["finished"]), _ptr(b["tokens"]),
+                                                              _ptr(b["out"]), None, None, 0, self._stream()), "eilev_rules_select")
+
+        return ("rules", float(repetition_penalty), ngram, int(min_new_tokens)), (lambda rows: {}), bind, None
+
+    def _decode_selected(self, selection, stats_name, inputs_embeds, attention_mask, max_new_tokens, eos_id, pad_id, start_id, use_graph, poll_every,
+                         trace, kv_dtype="bf16", **spec):
+        """The four device entry points: ``selection`` (_sampling_selection, _rules_selection) with ``spec`` on the OPT loop, or with a
+        ``start_id`` on the flan-t5 loop, whose ids begin with the start token, which the rules see (prefix_id) as hf's processors do.
+        More than 32 rows run in parts (the selection of the whole call is made first: its uniforms are drawn ONCE).  Records
+        ``stats_name`` = dict(path="device", steps=n)."""
+        t5, B = start_id is not None, inputs_embeds.shape[0]
+        start = torch.full((B, 1 if t5 else 0), int(start_id or 0), dtype=torch.int64, device=self.device)
+        if max_new_tokens <= 0:
+            return start
+        eos = eos_list(eos_id)
+        key, extra, bind, uniforms = selection(B, (self.t5dims if t5 else self.dims).vocab, max_new_tokens, int(start_id) if t5 else -1, eos, pad_id, **spec)
+        if B > 32:
+            if trace is not None:
+                raise ValueError("trace: at most 32 decode rows")
+            part = lambda i, j: spec if uniforms is None else dict(spec, generator=None, uniforms=uniforms[:, i:j])  # noqa: E731
+            ids = self._chunked_rows(lambda i, j: self._decode_selected(
+                selection, stats_name, inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, start_id, use_graph, poll_every, None,
+                kv_dtype, **part(i, j))[:, start.shape[1]:], B, pad_id, stats_name)
+            return torch.cat((start, ids), dim=1)
+        if t5:
+            ids = self._t5_select_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id,
+                                         lambda b, step_offset, finalize: bind(dict(b, **extra(B)), step_offset, finalize), use_graph, poll_every, trace)
+        else:
+            ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace,
+                                             kv_dtype)
+        setattr(self, stats_name, dict(path="device", steps=int(ids.shape[1])))
+        return torch.cat((start, ids), dim=1) if t5 else ids
+
     def sample_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, temperature=1.0, top_k=50, top_p=1.0,
                              repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None,
                              no_repeat_ngram_size=0, kv_dtype="bf16"):
-        """Multinomial sampling with the draw on the device (include/eilev_sample.h): _select_decode_device with eilev_sample_select after the
-        decode step, and eilev_rules_ban in front of it for ``no_repeat_ngram_size`` (hf applies the ban before the warpers).  ``eos_id``: an
-        id or up to 8 ids.  ``trace``: a list that receives a copy of every step's logits (use_graph=False; the n-gram ban is already written into them).  ``uniforms``:
-        (max_new, rows) in [0, 1) instead of the ones drawn from ``generator``.  Returns int64 (B, n) new tokens."""
-        from .sampling import eos_list
-
-        d = self.dims
-        B = inputs_embeds.shape[0]
-        if max_new_tokens <= 0:
-            return torch.empty((B, 0), dtype=torch.int64, device=self.device)
-        eos = eos_list(eos_id)
-        ngram = int(no_repeat_ngram_size or 0)
-        spec = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos,
-                    pad_id=pad_id, prefix_id=-1)
-        smp, uni_all, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, **spec)
-        if B > 32:
-            if trace is not None:
-                raise ValueError("trace: at most 32 decode rows")
-            return self._chunked_rows(lambda i, j: self.sample_decode_device(
-                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, temperature, top_k, top_p, repetition_penalty, min_new_tokens,
-                None, use_graph, poll_every, None, uni_all[:, i:j], ngram, kv_dtype), B, pad_id, "sample_stats")
-        rl, ban_params = self._rules_setup(d.vocab, max_new_tokens, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id) if ngram else (None, None)
-
-        def extra(rows):
-            return dict(uni=torch.empty((max_new_tokens, rows), dtype=torch.float32, device=self.device),
-                        scratch=torch.empty(int(smp.eilev_sample_scratch_bytes(rows, d.vocab)), dtype=torch.uint8, device=self.device))
-
-        def bind(ent):
-            state, finished, tokens, out, uni, scratch = ent["state"], ent["finished"], ent["tokens"], ent["out"], ent["uni"], ent["scratch"]
-            uni.copy_(uni_all)
-
-            def select(p_ban, p_draw):
-                def fn(lg):
-                    if ngram:
-                        self._rules_ban(rl, p_ban, lg, B, d.vocab, state, out)
-                    self._sample_select(smp, p_draw, lg, B, d.vocab, uni, state, finished, tokens, out, scratch)
-                return fn
-
-            # (the decode step has already advanced state[0]: step_offset -1, no finalize)
-            return select(ban_params(0, 0) if ngram else None, params(0, 1)), select(ban_params(-1, 0) if ngram else None, params(-1, 0))
-
-        key = ("sample", float(temperature), int(top_k or 0), float(top_p), float(repetition_penalty), int(min_new_tokens), ngram)
-        ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, extra, bind, use_graph, poll_every, trace,
-                                         kv_dtype)
-        self.sample_stats = dict(path="device", steps=int(ids.shape[1]))
-        return ids
+        """Multinomial sampling with the draw on the device (include/eilev_sample.h): _select_decode_device with _sampling_selection.
+        ``eos_id``: an id or up to 8 ids.  ``trace``: a list that receives a copy of every step's logits (use_graph=False; the n-gram ban is
+        already written into them).  ``uniforms``: (max_new, rows) in [0, 1) instead of the ones drawn from ``generator``.  Returns int64
+        (B, n) new tokens."""
+        return self._decode_selected(self._sampling_selection, "sample_stats", inputs_embeds, attention_mask, max_new_tokens, eos_id, pad_id, None,
+                                     use_graph, poll_every, trace, kv_dtype, temperature=temperature, top_k=top_k, top_p=top_p,
+                                     repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, generator=generator, uniforms=uniforms,
+                                     no_repeat_ngram_size=no_repeat_ngram_size)
 
     def rules_decode_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=-1, pad_id=1, repetition_penalty=1.0, no_repeat_ngram_size=0,
                             min_new_tokens=0, use_graph=True, poll_every=8, trace=None, kv_dtype="bf16"):
-        """Greedy search with logits rules on the device (include/eilev_rules.h): _select_decode_device with eilev_rules_select — repetition
-        penalty, n-gram ban, minimum length, up to 8 EOS ids, then the arg-max — after the decode step.  ``trace``: a list that receives a
-        copy of every step's logits (use_graph=False).  Returns int64 (B, n) new tokens."""
-        from .sampling import eos_list
-
-        d = self.dims
-        B = inputs_embeds.shape[0]
-        if max_new_tokens <= 0:
-            return torch.empty((B, 0), dtype=torch.int64, device=self.device)
-        eos = eos_list(eos_id)
-        ngram = int(no_repeat_ngram_size or 0)
-        rl, params = self._rules_setup(d.vocab, max_new_tokens, repetition_penalty=repetition_penalty, no_repeat_ngram=ngram, min_new=min_new_tokens,
-                                       eos_ids=eos, pad_id=pad_id, prefix_id=-1)
-        if B > 32:
-            if trace is not None:
-                raise ValueError("trace: at most 32 decode rows")
-            return self._chunked_rows(lambda i, j: self.rules_decode_device(
-                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, repetition_penalty, ngram, min_new_tokens, use_graph, poll_every,
-                kv_dtype=kv_dtype), B, pad_id, "rules_stats")
-
-        def bind(ent):
-            def select(p):
-                return lambda lg: self._rules_select(rl, p, lg, B, d.vocab, ent["state"], ent["finished"], ent["tokens"], ent["out"])
-            return select(params(0, 1)), select(params(-1, 0))
-
-        key = ("rules", float(repetition_penalty), ngram, int(min_new_tokens))
-        ids = self._select_decode_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, key, lambda rows: {}, bind, use_graph, poll_every,
-                                         trace, kv_dtype)
-        self.rules_stats = dict(path="device", steps=int(ids.shape[1]))
-        return ids
+        """Greedy search with logits rules on the device (include/eilev_rules.h): _select_decode_device with _rules_selection.  ``trace``: a
+        list that receives a copy of every step's logits (use_graph=False).  Returns int64 (B, n) new tokens."""
+        return self._decode_selected(self._rules_selection, "rules_stats", inputs_embeds, attention_mask, max_new_tokens, eos_id, pad_id, None,
+                                     use_graph, poll_every, trace, kv_dtype, repetition_penalty=repetition_penalty,
+                                     no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens)
 
     def _t5_select_device(self, inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id, bind, use_graph, poll_every, trace):
         """The flan-t5 decode loop: encoder and cross K/V once, then one decoder step + the caller's selection (position and bookkeeping read
-        from a device `state` word) captured into a hipGraph and replayed.  ``bind(state, finished, tokens, out) -> step(logits)``.  At most
+        from a device `state` word) captured into a hipGraph and replayed.  ``bind``: as in _select_decode_device, asked for (0, 1).  At most
         32 rows.  Returns the new ids (B, n), without the start token."""
         d = self.t5dims
         B = inputs_embeds.shape[0]
@@ -1454,7 +1366,7 @@ class HipEngine:
         out = torch.full((B, max_new_tokens), int(pad_id), dtype=torch.int64, device=self.device)
         logits = torch.empty((B, d.vocab), dtype=torch.float32, device=self.device)
         ws = self._workspace("t5dec", self.lib.eilev_t5_workspace_bytes(C.byref(d), B, 1, max(L, cap)))
-        step = bind(state, finished, tokens, out)
+        step = bind(dict(state=state, finished=finished, tokens=tokens, out=out), 0, 1)  # (every step selects and finalizes itself)
 
         def one_step():
             abi.check(self.lib.eilev_t5_decode_step(C.byref(d), C.byref(self.pack.t5), _ptr(tokens), _ptr(state), _ptr(am), B, _ptr(skv), cap,
@@ -1470,74 +1382,20 @@ class HipEngine:
     def t5_sample_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, temperature=1.0, top_k=50, top_p=1.0,
                          repetition_penalty=1.0, min_new_tokens=0, generator=None, use_graph=True, poll_every=8, trace=None, uniforms=None,
                          no_repeat_ngram_size=0):
-        """t5_greedy with eilev_sample_select in place of the arg-max (and eilev_rules_ban in front of it for ``no_repeat_ngram_size``):
-        decoder ids (B, 1 + n) INCLUDING the start token, which the rules see (prefix_id), as hf's processors do.  ``trace`` / ``uniforms``:
-        as sample_decode_device."""
-        from .sampling import eos_list
-
-        d = self.t5dims
-        B = inputs_embeds.shape[0]
-        start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
-        if max_new_tokens <= 0:
-            return start
-        eos = eos_list(eos_id)
-        ngram = int(no_repeat_ngram_size or 0)
-        smp, uni, params = self._sample_setup(B, d.vocab, max_new_tokens, generator, uniforms, temperature=temperature, top_k=top_k, top_p=top_p,
-                                              repetition_penalty=repetition_penalty, min_new=min_new_tokens, eos_ids=eos, pad_id=pad_id,
-                                              prefix_id=int(start_id))
-        if B > 32:
-            if trace is not None:
-                raise ValueError("trace: at most 32 decode rows")
-            ids = self._chunked_rows(lambda i, j: self.t5_sample_device(
-                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, start_id, temperature, top_k, top_p, repetition_penalty,
-                min_new_tokens, None, use_graph, poll_every, None, uni[:, i:j], ngram)[:, 1:], B, pad_id, "sample_stats")
-            return torch.cat((start, ids), dim=1)
-        rl, ban_params = self._rules_setup(d.vocab, max_new_tokens, no_repeat_ngram=ngram, eos_ids=eos, pad_id=pad_id,
-                                           prefix_id=int(start_id)) if ngram else (None, None)
-        scratch = torch.empty(int(smp.eilev_sample_scratch_bytes(B, d.vocab)), dtype=torch.uint8, device=self.device)
-        p_step, p_ban = params(0, 1), (ban_params(0, 0) if ngram else None)
-
-        def bind(state, finished, tokens, out):
-            def step(lg):
-                if ngram:
-                    self._rules_ban(rl, p_ban, lg, B, d.vocab, state, out)
-                self._sample_select(smp, p_step, lg, B, d.vocab, uni, state, finished, tokens, out, scratch)
-            return step
-
-        ids = self._t5_select_device(inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id, bind, use_graph, poll_every, trace)
-        self.sample_stats = dict(path="device", steps=int(ids.shape[1]))
-        return torch.cat((start, ids), dim=1)
+        """t5_greedy with _sampling_selection in place of the arg-max: decoder ids (B, 1 + n) INCLUDING the start token.  ``trace`` /
+        ``uniforms``: as sample_decode_device."""
+        return self._decode_selected(self._sampling_selection, "sample_stats", inputs_embeds, attention_mask, max_new_tokens, eos_id, pad_id, start_id,
+                                     use_graph, poll_every, trace, temperature=temperature, top_k=top_k, top_p=top_p,
+                                     repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, generator=generator, uniforms=uniforms,
+                                     no_repeat_ngram_size=no_repeat_ngram_size)
 
     def t5_rules_device(self, inputs_embeds, attention_mask, max_new_tokens, eos_id=1, pad_id=0, start_id=0, repetition_penalty=1.0,
                         no_repeat_ngram_size=0, min_new_tokens=0, use_graph=True, poll_every=8, trace=None):
-        """t5_greedy with eilev_rules_select in place of eilev_greedy_select: decoder ids (B, 1 + n) INCLUDING the start token, which the
-        rules see (prefix_id), as hf's processors do.  ``trace``: as rules_decode_device."""
-        from .sampling import eos_list
-
-        d = self.t5dims
-        B = inputs_embeds.shape[0]
-        start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
-        if max_new_tokens <= 0:
-            return start
-        eos = eos_list(eos_id)
-        ngram = int(no_repeat_ngram_size or 0)
-        rl, params = self._rules_setup(d.vocab, max_new_tokens, repetition_penalty=repetition_penalty, no_repeat_ngram=ngram, min_new=min_new_tokens,
-                                       eos_ids=eos, pad_id=pad_id, prefix_id=int(start_id))
-        if B > 32:
-            if trace is not None:
-                raise ValueError("trace: at most 32 decode rows")
-            ids = self._chunked_rows(lambda i, j: self.t5_rules_device(
-                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, eos_id, pad_id, start_id, repetition_penalty, ngram, min_new_tokens, use_graph,
-                poll_every)[:, 1:], B, pad_id, "rules_stats")
-            return torch.cat((start, ids), dim=1)
-        p_step = params(0, 1)
-        ids = self._t5_select_device(
-            inputs_embeds, attention_mask, max_new_tokens, eos, pad_id, start_id,
-            lambda state, finished, tokens, out: (lambda lg: self._rules_select(rl, p_step, lg, B, d.vocab, state, finished, tokens, out)),
-            use_graph, poll_every, trace)
-        self.rules_stats = dict(path="device", steps=int(ids.shape[1]))
-        return torch.cat((start, ids), dim=1)
-
+        """t5_greedy with _rules_selection in place of eilev_greedy_select: decoder ids (B, 1 + n) INCLUDING the start token.  ``trace``: as
+        rules_decode_device."""
+        return self._decode_selected(self._rules_selection, "rules_stats", inputs_embeds, attention_mask, max_new_tokens, eos_id, pad_id, start_id,
+                                     use_graph, poll_every, trace, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                     min_new_tokens=min_new_tokens)
 
     # ---- encoder-decoder LM (flan-t5) ------------------------------------------------------------------------
     def t5_encode(self, inputs_embeds, attention_mask):
@@ -1624,15 +1482,13 @@ class HipEngine:
         """Greedy generation for the encoder-decoder LM [ref:eilev/model/v2.py:318-322 -> hf _sample]: returns decoder ids
         (B, 1 + n) INCLUDING the start token, like HF does for encoder-decoder models.  _t5_select_device with eilev_greedy_select as
         the selection."""
-        from .sampling import eos_list
-
         B, vocab = inputs_embeds.shape[0], self.t5dims.vocab
         start = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.device)
         if max_new_tokens <= 0:
             return start
         ids = self._t5_select_device(
             inputs_embeds, attention_mask, max_new_tokens, eos_list(eos_id), pad_id, start_id,
-            lambda state, finished, tokens, out: (lambda lg: self._greedy_select(lg, B, vocab, state, finished, eos_id, pad_id, tokens, out)),
+            lambda b, step_offset, finalize: (lambda lg: self._greedy_select(lg, B, vocab, b["state"], b["finished"], eos_id, pad_id, b["tokens"], b["out"])),
             use_graph, poll_every, None)
         return torch.cat((start, ids), dim=1)
 
@@ -1640,17 +1496,8 @@ class HipEngine:
         """t5_greedy with prompt-lookup drafts (batch 1): returns the decoder ids of t5_greedy, start id included.  The corpus is the
         encoder's text ids (``text_ids``), then the generated decoder ids.  Each step verifies [last, d1 .. dm] with eilev_t5_decode
         (past_len = committed count) or runs eilev_t5_decode_step when there is no draft.  Counters of the call: ``self.pld_stats``."""
-        from .pld import lookup_loop
-        from .sampling import eos_list
-
         d = self.t5dims
-        B = inputs_embeds.shape[0]
-        if B != 1:
-            raise ValueError("assisted generate is only supported for batch_size = 1")
-        k, n_new = int(num_tokens), int(max_new_tokens)
-        if not 1 <= k <= abi.PLD_MAX_K or int(ngram) < 1:
-            raise ValueError(f"prompt_lookup_num_tokens must be in 1..{abi.PLD_MAX_K} and max_matching_ngram_size >= 1")
-        self.pld_stats = dict(verify=0, single=0, accepted=0)
+        k, n_new = self._lookup_head(inputs_embeds.shape[0], num_tokens, ngram, max_new_tokens)
         enc = self.t5_encode(inputs_embeds, attention_mask)
         ckv = self.t5_cross_kv(enc)
         L = enc.shape[1]
@@ -1678,8 +1525,8 @@ class HipEngine:
 
         abi.check(pld.eilev_pld_draft(C.byref(params), _ptr(b["corpus"]), _ptr(b["corpus_len"]), _ptr(window), _ptr(b["status"]), self._stream()),
                   "eilev_pld_draft")
-        c = lookup_loop(b["status"].tolist(), verify, single, lambda lg, rows: self._pld_commit(pld, params, b, lg, rows, d.vocab), self.pld_stats)
-        return torch.cat((start, out[:c].reshape(1, c)), dim=1)
+        ids = self._lookup_tail(b["status"].tolist(), verify, single, lambda lg, rows: self._pld_commit(pld, params, b, lg, rows, d.vocab), out)
+        return torch.cat((start, ids), dim=1)
 
     def t5_beam(self, inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty=1.0, eos_id=1, pad_id=0, start_id=0,
                 early_stopping=False, num_return_sequences=1, sampler=None, min_new_tokens=0, rules=None, use_graph=True):
@@ -1690,44 +1537,24 @@ class HipEngine:
         Everything else (beam-search sampling, user processors, stopping criteria, num_beams == 1, other head sizes, ``beam_device_loop =
         False``) keeps the host loop: the cross K/V replicated to the beams, every step reorders the self-attention cache rows by the
         surviving beams' parents and runs eilev_t5_decode on all rows.  ``self.t5_beam_stats`` = dict(path="device" | "host", steps=n)."""
-        from .beam import beam_search
-        from .sampling import eos_list
-
-        # hf generation/utils.py:3319 `output_fill_value = pad_token_id or eos_token_id[0] ...`: a pad id of 0 (T5) is falsy,
-        # so finished hypotheses are padded with the EOS id
-        if pad_id == 0 and num_beams > 1:
-            e = eos_list(eos_id)
-            pad_id = e[0] if e else -1
+        plan = route.plan_decode(route.Caps.of(self), num_beams, sampler, rules, eos_id, min_new_tokens, max_new_tokens, False, in_search_loop=True)
+        # hf generation/utils.py:3319 `output_fill_value = pad_token_id or eos_token_id[0] ...`: T5's pad id 0 is falsy, finished hypotheses get the EOS id
+        if pad_id == 0 and plan.pad_from_eos:
+            pad_id = (eos_list(eos_id) or [-1])[0]
         d = self.t5dims
-        with_rules, rules_kw, rules_in = False, None, rules
-        eos_l = eos_list(eos_id)
-        topk_ok, advance_ok = self._beam_kernels_ok(d.vocab, num_beams, eos_l, max(1, max_new_tokens))
-        device_loop = sampler is None and 1 < num_beams <= 32 and max_new_tokens > 0 and self.beam_device_loop and abi.t5beam_supported(d)
-        if sampler is None or sampler.get("greedy") or num_beams > 1:
-            # greedy search with rules runs on the device (t5_rules_device), and so does beam search when it takes the fused form of the device
-            # loop; else the rules, numbers included, run in the host loop
-            greedy1 = sampler is not None and num_beams == 1
-            min_new = int(sampler.get("min_new_tokens", 0) or 0) if sampler is not None else int(min_new_tokens)
-            rules_kw, rules, with_rules = self._route_rules(rules, d.vocab, eos_id, min_new, allow_device=greedy1 or (device_loop and advance_ok))
-            if rules_kw is not None and greedy1:
-                return self.t5_rules_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, start_id=start_id, **rules_kw)
-        if device_loop and (rules_kw is not None or (not rules and int(min_new_tokens) == 0)):
-            per = max(1, 32 // num_beams)
-            if inputs_embeds.shape[0] > per:  # at most 32 decode rows per call: sample group by sample group (every part is routed again)
-                return self._chunked_rows(lambda i, j: self.t5_beam(
-                    inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, num_beams, length_penalty, eos_id, pad_id, start_id, early_stopping,
-                    num_return_sequences, None, min_new_tokens, rules_in, use_graph), inputs_embeds.shape[0], pad_id, "t5_beam_stats", per=per)
+        device = dict(sample_device=self.t5_sample_device, rules_device=self.t5_rules_device).get(plan.route)
+        if device is not None:
+            return device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, start_id=start_id, **plan.dev_kw)
+        if plan.chunk and inputs_embeds.shape[0] > plan.chunk:  # at most 32 decode rows per call: sample group by sample group, each planned again
+            return self._chunked_rows(lambda i, j: self.t5_beam(
+                inputs_embeds[i:j], attention_mask[i:j], max_new_tokens, num_beams, length_penalty, eos_id, pad_id, start_id, early_stopping,
+                num_return_sequences, sampler, min_new_tokens, rules, use_graph), inputs_embeds.shape[0], pad_id, "t5_beam_stats", per=plan.chunk)
+        if plan.route == "beam_device":
             return self._t5_beam_device(inputs_embeds, attention_mask, max_new_tokens, num_beams, length_penalty, eos_id, pad_id, start_id,
-                                        early_stopping, num_return_sequences, use_graph, rules_kw, topk_ok, advance_ok)
-        if sampler is not None and num_beams == 1:
-            dev_kw = None
-            if not sampler.get("greedy"):
-                sampler, rules, dev_kw = self._route_sampling(sampler, rules, d.vocab, eos_id)
-            if dev_kw is not None:
-                return self.t5_sample_device(inputs_embeds, attention_mask, max_new_tokens, eos_id=eos_id, pad_id=pad_id, start_id=start_id, **dev_kw)
-            if rules and rules.get("processors") is not None and rules.get("prefix") is None:  # hf's processors see the start token
-                rules = dict(rules)  # (the caller's dict stays as it is)
-                rules["prefix"] = torch.full((inputs_embeds.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
+                                        early_stopping, num_return_sequences, use_graph, plan.dev_kw, plan.topk_ok, plan.advance_ok)
+        if plan.start_prefix:  # hf's processors see the start token (the plan's own copy of the rules: the caller's dict stays as it is)
+            plan = plan._replace(rules=dict(plan.rules, prefix=torch.full((inputs_embeds.shape[0], 1), int(start_id), dtype=torch.int64,
+                                                                          device=self.device)))
         enc = self.t5_encode(inputs_embeds, attention_mask)
         B, L, _ = enc.shape
         R = B * num_beams
@@ -1746,14 +1573,8 @@ class HipEngine:
             steps[0] += 1
             return self.t5_decode(next_tokens.view(R, 1), am, steps[0], skv, cap, ckv, L)[:, 0]
 
-        if sampler is not None and num_beams == 1:
-            from .sampling import sample_loop
-
-            ids = sample_loop(step, first, max_new_tokens, eos_id, pad_id, **sampler, **{k: v for k, v in (rules or {}).items() if k != "fill_id"})
-        else:
-            ids = beam_search(step, first[::num_beams].contiguous(), B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id,
-                              early_stopping, num_return_sequences, sampler=sampler, min_new_tokens=min_new_tokens, **(rules or {}))
-        self._host_stats(ids, sampler, num_beams, with_rules)
+        ids = self._host_loop(plan, step, first[::num_beams].contiguous(), B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id,
+                              early_stopping, num_return_sequences, min_new_tokens)
         self.t5_beam_stats = dict(path="host", steps=int(ids.shape[1]))
         head = torch.full((ids.shape[0], 1), int(start_id), dtype=torch.int64, device=self.device)
         return torch.cat((head, ids), dim=1)

@@ -9,9 +9,11 @@ state-dict names; none of them has arithmetic in its ``forward``
 ``forward`` or ``generate`` on a model that is not on an AMD GPU raises.
 
 Not built (raise ``NotImplementedError``): contrastive / group-beam decoding (greedy, multinomial sampling, beam search and beam-search sampling
-are).  ``generate`` takes ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_new_tokens`` and several EOS ids as numbers: greedy search, sampling and
-beam search apply them on the device in the decode step, for OPT and for flan-t5 (whose beam search runs on the device at head size 64, without
-copying or replicating a cache: include/eilev_t5beam.h); beam-search sampling and user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
+are).  ``generate`` reads as parse (``_parse_generate``: every keyword and argument check, no engine, no GPU), refuse, encode, execute; which route a call
+takes — the captured greedy step, the device draw, the device rules, the fused beam loop or a host loop — is decided in eilev_amd/route.py ``plan_decode``
+alone, for OPT and flan-t5, and the ``kv_cache_dtype="fp8"`` refusal is derived from that plan before any encode.  ``repetition_penalty``,
+``no_repeat_ngram_size``, ``min_new_tokens`` and several EOS ids go as numbers and run on the device in the decode step (flan-t5's beam search at head size
+64, without copying or replicating a cache: include/eilev_t5beam.h); beam-search sampling and user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
 ``encode_context`` prefills a leading part that many calls share — the in-context examples — once; ``generate(context=...)`` and
 ``classify(share_prompt_cache=True)`` then run their rows over that one cached prefix (include/eilev_prefix.h; plain greedy search on OPT).
 ``generate(kv_cache_dtype="fp8")`` keeps the OPT decode step's KV cache in e4m3 bytes with power-of-two scales (include/eilev_kv8.h; greedy
@@ -20,6 +22,8 @@ search, sampling and the logits rules on their device routes).
 the Q-Former (self- and cross-attention weights), the OPT language model and the T5 stacks (hidden states; self- and cross-attention weights).  ``decoder_attention_mask`` with padding is honoured on the evaluation route (the first target position of a row must stay visible).
 """
 from __future__ import annotations
+
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -500,15 +504,9 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         return Blip2ForConditionalGenerationModelOutput(loss=loss, logits=logits, vision_outputs=vis_out, qformer_outputs=qf_out,
                                                         language_model_outputs=lm_out)
 
-    @torch.no_grad()
-    def generate(self, input_ids, pixel_values=None, video_input_mask=None, attention_mask=None, **generate_kwargs):
-        """Greedy decoding on the HIP path; returns only the NEW tokens like the reference does for OPT
-        (ref:eilev/model/v2.py:254-324 drives the LM with inputs_embeds)."""
-        assert not (input_ids is None and pixel_values is None)
-        if pixel_values is not None:
-            assert video_input_mask is not None
-        if hasattr(self, "hf_device_map"):
-            self._preprocess_accelerate()
+    def _parse_generate(self, input_ids, generate_kwargs):
+        """generate()'s keywords as one request, every argument check included; touches neither the engine nor the GPU.  ``sampler``,
+        ``rules`` and ``eos_arg`` are in the form the engine takes them (eilev_amd/route.py plan_decode)."""
         kw = dict(generate_kwargs)
         context = kw.pop("context", None)  # a VideoContext: input_ids / pixel_values describe only what follows it
         # "fp8": the decode steps keep their KV cache in e4m3 bytes with power-of-two scales (include/eilev_kv8.h); None / "bf16": the default
@@ -582,7 +580,7 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         if not user_procs:
             # the only processors of the call: the engine takes them as numbers — the device paths apply them in the captured step
             # (include/eilev_sample.h, include/eilev_rules.h), the host loops wrap them into the same transformers processors again
-            # (engine._route_sampling, engine._route_rules)
+            # (eilev_amd/route.py)
             numbers = {k: v for k, v in (("repetition_penalty", rp), ("no_repeat_ngram_size", ngram)) if v is not None}
             if sampler is not None and num_beams == 1:
                 sampler.update(numbers)
@@ -641,98 +639,91 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             if context.P + input_ids.shape[1] + int(max_new) > limit:
                 raise ValueError(f"context ({context.P}) + input_ids ({input_ids.shape[1]}) + max_new_tokens ({int(max_new)}) exceed "
                                  f"max_position_embeddings ({limit})")
-        if kv_dtype == "fp8":  # served by the three captured device routes of the OPT decode step; everything is checked here, before any encode
-            from .. import abi as _abi
+        # the plain captured step knows ONE eos id and no minimum length; several ids, 0 < min_new_tokens < max_new_tokens,
+        # repetition_penalty and no_repeat_ngram_size go to the engine with the call: it applies them in the captured step
+        # (include/eilev_rules.h) or, with user processors / stopping criteria, in the host loops (eilev_amd/sampling.py, beam.py)
+        eos1 = int(eos_ids[0]) if eos_ids else -1
+        with_rules = len(eos_ids) > 1 or min_new > 0 or rules is not None
+        if num_beams == 1:  # one row per prompt: greedy search is asked of the engine as a greedy sampler, which carries min_new_tokens
+            sampler = dict(sampler if sampler is not None else dict(greedy=True), min_new_tokens=min_new)
+        return SimpleNamespace(context=context, kv_dtype=kv_dtype, num_beams=num_beams, do_sample=do_sample, length_penalty=float(length_penalty),
+                               early_stopping=early_stopping, num_return=int(num_return), sampler=sampler, max_new=int(max_new), min_new=min_new,
+                               eos_ids=eos_ids, eos1=eos1, eos_arg=eos_ids if with_rules else eos1, pad=int(pad), rules=rules, lookup=lookup,
+                               lookup_ngram=lookup_ngram, want_dict=want_dict, want_scores=want_scores, want_logits=want_logits)
 
-            t_cfg = self.config.text_config
-            heads = int(getattr(t_cfg, "num_attention_heads", 0) or 0)
-            head_ok = not self._is_t5 and heads > 0 and int(t_cfg.hidden_size) // heads in (80, 128)
-            eng0 = self._hip[1] if self._hip is not None else None  # (an engine that exists: its route switches; a new one has both on)
-            with_rules0 = len(eos_ids) > 1 or min_new > 0 or rules is not None
-            combo = [n for n, on in (("the flan-t5 language model", self._is_t5), ("num_beams > 1", num_beams > 1), ("context=", context is not None),
-                                     ("prompt_lookup_num_tokens", lookup is not None),
-                                     ("a head size other than 80 / 128", not self._is_t5 and not head_ok),
-                                     ("logits_processor (a host loop)", bool(user_procs)),
-                                     ("stopping criteria / max_time (a host loop)", len(crit) > 0),
-                                     ("more than 8 EOS ids (a host loop)", len(eos_ids) > min(_abi.SAMPLE_MAX_EOS, _abi.RULES_MAX_EOS)),
-                                     ("a vocabulary the device selection does not take (a host loop)",
-                                      (sampler is not None or with_rules0) and not (_abi.sample_supported(t_cfg.vocab_size) and _abi.rules_supported(t_cfg.vocab_size))),
-                                     ("device_sampling off (a host loop)", sampler is not None and not getattr(eng0, "device_sampling", True)),
-                                     ("device_rules off (a host loop)", sampler is None and with_rules0 and not getattr(eng0, "device_rules", True))) if on]
-            if combo:
+    @torch.no_grad()
+    def generate(self, input_ids, pixel_values=None, video_input_mask=None, attention_mask=None, **generate_kwargs):
+        """Decoding on the HIP path: parse, refuse, encode, execute.  Returns only the NEW tokens like the reference does for OPT
+        (ref:eilev/model/v2.py:254-324 drives the LM with inputs_embeds)."""
+        from .. import route
+
+        assert not (input_ids is None and pixel_values is None)
+        if pixel_values is not None:
+            assert video_input_mask is not None
+        if hasattr(self, "hf_device_map"):
+            self._preprocess_accelerate()
+        r = self._parse_generate(input_ids, generate_kwargs)
+        # the route, before any encode: from the engine that exists (its switches), else from the configuration (a new engine has them on)
+        caps = route.Caps.of_config(self.config, self._hip[1] if self._hip is not None else None)
+        plan = route.plan_decode(caps, r.num_beams, r.sampler, r.rules, r.eos_arg, r.min_new, r.max_new, False, r.kv_dtype)
+        if r.kv_dtype == "fp8":  # served by the three captured routes of the OPT decode step
+            said = {"user processor": "logits_processor", "stopping criterion": "stopping criteria / max_time", "more than 8 EOS ids": "more than 8 EOS ids",
+                    "vocabulary not taken": "a vocabulary the device selection does not take"}
+            combo = [n for n, on in (("the flan-t5 language model", self._is_t5), ("num_beams > 1", "beams" in plan.host_reasons),
+                                     ("context=", r.context is not None), ("prompt_lookup_num_tokens", r.lookup is not None),
+                                     ("a head size other than 80 / 128", not self._is_t5 and caps.head_size not in (80, 128))) if on]
+            combo += [f"{said[n]} (a host loop)" for n in plan.host_reasons if n in said]
+            combo += [f"{s} off (a host loop)" for s in plan.switches_off if s in ("device_sampling", "device_rules")]
+            if combo or plan.route not in route.CAPTURED:
                 raise NotImplementedError(f"generate(kv_cache_dtype='fp8') with {', '.join(combo)} is not built on the HIP path (greedy search, sampling "
                                           "and the logits rules of the captured OPT decode step are)")
-        if want_dict and not (want_scores or want_logits):  # sequences only: any decoding mode, wrapped like hf wraps it
+        if r.want_dict and not (r.want_scores or r.want_logits):  # sequences only: any decoding mode, wrapped like hf wraps it
             from transformers.generation.utils import GenerateDecoderOnlyOutput, GenerateEncoderDecoderOutput
 
             plain = {k: v for k, v in generate_kwargs.items() if k not in ("return_dict_in_generate", "output_scores", "output_logits")}
             seq = self.generate(input_ids, pixel_values=pixel_values, video_input_mask=video_input_mask, attention_mask=attention_mask, **plain)
             return (GenerateEncoderDecoderOutput if self._is_t5 else GenerateDecoderOnlyOutput)(sequences=seq)
-        if num_beams == 1 and not do_sample and int(num_return) != 1:
+        if r.num_beams == 1 and not r.do_sample and r.num_return != 1:
             raise ValueError("Greedy methods without beam search do not support `num_return_sequences` different than 1")
-        if num_beams > 1 and int(num_return) > num_beams:
+        if r.num_beams > 1 and r.num_return > r.num_beams:
             raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         emb, _, _ = self._encode(pixel_values, input_ids, video_input_mask)
-        if sampler is not None and num_beams == 1 and int(num_return) > 1:
+        if r.do_sample and r.num_beams == 1 and r.num_return > 1:
             # hf `_expand_inputs_for_generation`: every prompt is repeated num_return_sequences times (rows of one prompt adjacent)
-            emb = emb.repeat_interleave(int(num_return), dim=0)
-            attention_mask = attention_mask.repeat_interleave(int(num_return), dim=0)
-        # the plain captured step knows ONE eos id and no minimum length; several ids, 0 < min_new_tokens < max_new_tokens,
-        # repetition_penalty and no_repeat_ngram_size go to the engine with the call: it applies them in the captured step
-        # (include/eilev_rules.h) or, with user processors / stopping criteria, in the host loops (eilev_amd/sampling.py, beam.py)
-        eos1 = eos_ids[0] if eos_ids else -1
-        with_rules = len(eos_ids) > 1 or min_new > 0 or rules is not None
+            emb = emb.repeat_interleave(r.num_return, dim=0)
+            attention_mask = attention_mask.repeat_interleave(r.num_return, dim=0)
         eng = self.engine()
-        if context is not None:
-            return self._generate_after_context(eng, context, emb, attention_mask, int(max_new), int(eos1), int(pad))
-        if lookup is not None:  # the corpus: the row's visible text ids (no left padding, no video placeholder)
+        if r.context is not None:
+            return self._generate_after_context(eng, r.context, emb, attention_mask, r.max_new, r.eos1, r.pad)
+        t = self.config.text_config
+        # what the two language models' entry points take beside the common arguments: flan-t5 its decoder start token, OPT the kv dtype
+        start = dict(start_id=int(t.decoder_start_token_id if t.decoder_start_token_id is not None else t.pad_token_id)) if self._is_t5 else {}
+        lm_kw = start if self._is_t5 else dict(kv_dtype=r.kv_dtype)
+        if r.lookup is not None:  # the corpus: the row's visible text ids (no left padding, no video placeholder)
             keep = attention_mask[0] != 0
             if video_input_mask is not None:
                 keep = keep & (video_input_mask[0] == 0)
             text = input_ids[0][keep.to(input_ids.device)]
-            if self._is_t5:
-                t = self.config.text_config
-                start = t.decoder_start_token_id if t.decoder_start_token_id is not None else t.pad_token_id
-                return eng.t5_greedy_lookup(emb, attention_mask, text, int(max_new), lookup, lookup_ngram, eos_id=eos_ids, pad_id=int(pad),
-                                            start_id=int(start))
-            return eng.greedy_lookup_decode(emb, attention_mask, text, int(max_new), lookup, lookup_ngram, eos_id=eos_ids, pad_id=int(pad))
-        if want_dict:
-            plain_greedy = num_beams == 1 and sampler is None and not with_rules
-            if (want_scores or want_logits) and not (plain_greedy and not self._is_t5):
+            return (eng.t5_greedy_lookup if self._is_t5 else eng.greedy_lookup_decode)(
+                emb, attention_mask, text, r.max_new, r.lookup, r.lookup_ngram, eos_id=r.eos_ids, pad_id=r.pad, **start)
+        if r.want_dict:  # (the sequences-only form returned before the encode)
+            if self._is_t5 or plan.route != "greedy":
                 raise NotImplementedError("generate(output_scores / output_logits) is served for greedy search on the decoder-only language model only")
             from transformers.generation.utils import GenerateDecoderOnlyOutput
 
-            if plain_greedy and not self._is_t5 and (want_scores or want_logits):
-                ids, steps = eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad), use_graph=False, return_step_logits=True,
-                                               kv_dtype=kv_dtype)
-                steps = tuple(st_[:, : self.config.text_config.vocab_size].float() for st_ in steps[: ids.shape[1]])
-                return GenerateDecoderOnlyOutput(sequences=ids, scores=steps if want_scores else None, logits=steps if want_logits else None)
-            raise AssertionError("unreachable: the sequences-only form returned before the encode")
-        if self._is_t5:
-            t = self.config.text_config
-            start = t.decoder_start_token_id if t.decoder_start_token_id is not None else t.pad_token_id
-            if rules is not None:  # hf's processors see the decoder ids, which begin with the start token
-                rules["prefix"] = torch.full((emb.shape[0], 1), int(start), dtype=torch.int64, device=emb.device)
-            if num_beams > 1:
-                return eng.t5_beam(emb, attention_mask, int(max_new), num_beams, float(length_penalty), eos_id=eos_ids if with_rules else eos1,
-                                   pad_id=int(pad), start_id=int(start), early_stopping=early_stopping,
-                                   num_return_sequences=int(num_return), sampler=sampler, min_new_tokens=min_new, rules=rules)
-            if sampler is not None or with_rules:
-                rule = dict(sampler) if sampler is not None else dict(greedy=True)
-                return eng.t5_beam(emb, attention_mask, int(max_new), 1, eos_id=eos_ids if with_rules else eos1, pad_id=int(pad),
-                                   start_id=int(start), sampler=dict(rule, min_new_tokens=min_new), rules=rules)
-            return eng.t5_greedy(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad), start_id=int(start))
-        if num_beams > 1:
-            return eng.beam_decode(emb, attention_mask, int(max_new), num_beams, float(length_penalty), eos_id=eos_ids if with_rules else eos1,
-                                   pad_id=int(pad), early_stopping=early_stopping, num_return_sequences=int(num_return), sampler=sampler,
-                                   min_new_tokens=min_new, rules=rules)
-        if sampler is not None or with_rules:
-            rule = dict(sampler) if sampler is not None else dict(greedy=True)
-            return eng.beam_decode(emb, attention_mask, int(max_new), 1, eos_id=eos_ids if with_rules else eos1, pad_id=int(pad),
-                                   sampler=dict(rule, min_new_tokens=min_new), rules=rules, kv_dtype=kv_dtype)
-        return eng.greedy_decode(emb, attention_mask, int(max_new), eos_id=int(eos1), pad_id=int(pad), kv_dtype=kv_dtype)
+            ids, steps = eng.greedy_decode(emb, attention_mask, r.max_new, eos_id=r.eos1, pad_id=r.pad, use_graph=False, return_step_logits=True,
+                                           kv_dtype=r.kv_dtype)
+            steps = tuple(st_[:, : t.vocab_size].float() for st_ in steps[: ids.shape[1]])
+            return GenerateDecoderOnlyOutput(sequences=ids, scores=steps if r.want_scores else None, logits=steps if r.want_logits else None)
+        if plan.route == "greedy":
+            return (eng.t5_greedy if self._is_t5 else eng.greedy_decode)(emb, attention_mask, r.max_new, eos_id=r.eos1, pad_id=r.pad, **lm_kw)
+        if self._is_t5 and r.rules is not None:  # hf's processors see the decoder ids, which begin with the start token
+            r.rules["prefix"] = torch.full((emb.shape[0], 1), start["start_id"], dtype=torch.int64, device=emb.device)
+        return (eng.t5_beam if self._is_t5 else eng.beam_decode)(
+            emb, attention_mask, r.max_new, r.num_beams, r.length_penalty, eos_id=r.eos_arg, pad_id=r.pad, early_stopping=r.early_stopping,
+            num_return_sequences=r.num_return if r.num_beams > 1 else 1, sampler=r.sampler, min_new_tokens=r.min_new, rules=r.rules, **lm_kw)
 
     @torch.no_grad()
     def encode_context(self, input_ids, pixel_values=None, video_input_mask=None) -> VideoContext:

@@ -261,9 +261,12 @@ def test_unsupported_vocabulary_goes_to_the_host_loop():
     assert rc == -2  # EILEV_E_UNSUPPORTED
     _, _, eng = models("mid")
     sampler = dict(temperature=1.0, top_k=50, top_p=1.0, generator=None)
-    assert eng._route_sampling(sampler, None, 1002, -1)[2] is None
-    assert eng._route_sampling(sampler, None, 1000, -1)[2] is not None
-    assert eng._route_sampling(sampler, None, 1000, list(range(9)))[2] is None  # more than 8 EOS ids
+    from eilev_amd.route import Caps, plan_decode
+
+    dev_kw = lambda vocab, eos_id: plan_decode(Caps.of(eng)._replace(vocab=vocab), 1, sampler, None, eos_id, 0, 8, False).dev_kw
+    assert dev_kw(1002, -1) is None
+    assert dev_kw(1000, -1) is not None
+    assert dev_kw(1000, list(range(9))) is None  # more than 8 EOS ids
 
 
 def test_engine_reports_the_host_path_for_an_unsupported_vocabulary(monkeypatch):

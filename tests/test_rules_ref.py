@@ -281,16 +281,23 @@ def test_library_exports_exactly_the_header():
 
 
 def test_routing_on_a_stub():
-    """engine._route_rules without an engine: the numeric case goes to the device; more than 8 EOS ids, a vocabulary the library does not
+    """route.plan_decode without an engine: the numeric case goes to the device; more than 8 EOS ids, a vocabulary the library does not
     take, a user processor, a stopping criterion, a trace or the switch send it to the host with transformers' processors rebuilt."""
-    from types import SimpleNamespace
-
     from transformers import NoRepeatNGramLogitsProcessor, RepetitionPenaltyLogitsProcessor
 
-    from eilev_amd.engine import HipEngine
+    from eilev_amd.route import Caps, plan_decode
 
-    eng = SimpleNamespace(device_rules=True, _host_processors=HipEngine._host_processors)
-    route = lambda *a, **k: HipEngine._route_rules(eng, *a, **k)
+    eng = dict(device_rules=True)
+
+    def route(rules, vocab, eos_id, min_new_tokens=0, trace=None, allow_device=True):
+        """(device keywords, host-form rules, with_rules) of a greedy search call: asked as the greedy sampler of num_beams == 1, which the
+        device takes; ``allow_device=False``: asked as a one-beam search, which it does not."""
+        sampler = dict(greedy=True, min_new_tokens=min_new_tokens) if allow_device else None
+        plan = plan_decode(Caps("opt", vocab, 80, device_rules=eng["device_rules"]), 1, sampler, rules, eos_id, min_new_tokens, 8, trace is not None,
+                           in_search_loop=True)
+        assert (plan.route == "rules_device") == (plan.dev_kw is not None)
+        return plan.dev_kw, plan.rules, plan.with_rules
+
     nums = dict(repetition_penalty=1.5, no_repeat_ngram_size=3)
     kw, rules, on = route(dict(nums), 50272, [2, 5], 2)
     assert kw == dict(repetition_penalty=1.5, no_repeat_ngram_size=3, min_new_tokens=2) and rules is None and on
@@ -311,5 +318,5 @@ def test_routing_on_a_stub():
     rules = host(dict(nums, processors=[user], stopping=None), 50272, 2)
     assert len(rules["processors"]) == 3 and rules["processors"][2] is user
     assert host(dict(processors=None, stopping=lambda ids, scores: False), 50272, 2)["stopping"] is not None
-    eng.device_rules = False
+    eng["device_rules"] = False
     assert host(dict(nums), 50272, 2)["processors"] is not None
