@@ -61,7 +61,33 @@ __device__ __forceinline__ void tile_coords(const GemmArgs &g, int tiles_m, int 
     tn = in / gsz;
 }
 
-// Epilogue shared by every tiled kernel.  acc[i][j][reg] = C[m = i*32 + (lane & 31)][n = j*32 + (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5)].
+// Tile list of the persistent kernel's 16 x 16 instances when N % 256 == 128 (gemm_pp4.h TALL; N = 1408 = 5.5 x 256): the whole-tile region is
+// ceil(M / 256) x floor(N / 256) tiles of 256 x 256 as above, the half column is ceil(M / 384) TALL tiles of 384 rows x 128 columns (a K-step
+// of one stages 384 + 128 rows: one step buffer, like a whole tile, for 0.75 of its MFMAs — a 256 x 128 half tile staged 0.75 of it for 0.5).
+// Groups stay 4 row tiles high (1024 rows = 2 2/3 tall tiles): a group's 4 x floor(N / 256) whole tiles column by column as above, then the
+// tall tiles that START in its rows — 3, 3, 2 per three groups, so a tall tile runs next to the row tiles whose A rows it shares (the third
+// of a group reaches 128 rows into the next one).  The last group has 1..4 row tiles and the tall tiles that are left.  Same XCD ranges.
+// (Groups of 3 row tiles = 2 whole tall tiles were built first: the parent's own tile list at 3 rows per group loses 2.6 % on fc2 and 3.1 %
+// on proj, and with it the tall tiles gave fc2 +0.7 %, proj -3.3 %; groups of 6: fc2 -1.4 %, proj -5 %: profiles/tall_tiles_groups_ab.log.)
+__host__ __device__ __forceinline__ int tall_ntiles(int M, int N) { return ((M + 255) / 256) * (N / 256) + (M + 383) / 384; }
+__device__ __forceinline__ void tile_coords_tall(const GemmArgs &g, int &m0, int &n0, int t = blockIdx.x) {
+    const int tiles_m = (g.M + 255) / 256, tn_full = g.N / 256, nwg = tall_ntiles(g.M, g.N);
+    const int xcd = t & 7, q = nwg >> 3, r = nwg & 7;
+    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (t >> 3);
+    // three groups = 12 tn_full + 8 tiles; tall tiles before group i: ceil(8 i / 3)
+    const int gfull = 4 * tn_full + 3, period = 3 * gfull - 1, sup = t / period, rem = t - sup * period;
+    const int gi = rem >= 2 * gfull ? 2 : rem >= gfull ? 1 : 0, group = sup * 3 + gi, first = group * 4, in = rem - gi * gfull;
+    const int gsz = min(tiles_m - first, 4), whole = gsz * tn_full;
+    if (in < whole) {
+        m0 = (first + in % gsz) * 256;
+        n0 = (in / gsz) * 256;
+    } else {  // (t < nwg: in the last group in - whole stays below the number of tall tiles that are left)
+        m0 = ((8 * group + 2) / 3 + in - whole) * 384;
+        n0 = tn_full * 256;
+    }
+}
+
+// Epilogue shared by every tiled kernel. acc[i][j][reg] = C[m = i*32 + (lane & 31)][n = j*32 + (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5)].
 // bf16 output: each wave stages its rows [IBEG*32, IEND*32) x WN in a private LDS region so that HBM sees whole
 // 128-byte row segments, 16 bytes per lane (2-byte stores straight from the MFMA layout cost as much as the K
 // loop): (a) residual rows -> LDS (coalesced); (b) acc + bias, activation, + residual -> bf16 in place;

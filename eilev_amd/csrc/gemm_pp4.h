@@ -33,9 +33,21 @@ template <int EPI, bool F8 = false, int LN = 0, int M16K = 0, bool A3 = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     // M16K: 0 = 32 x 32 x 16 MFMAs; 1 = 16 x 16 x 32, a half-valid last column tile runs as a WHOLE tile (its W rows past N are not staged:
     // stale, finite LDS bytes; the waves that own columns >= N skip the epilogue) — no half-tile code in the instance: the folded-LayerNorm
-    // consumers, whose registers are tightest (qkv, N = 4224: 3 % padding, +2.1 %); 2 = 16 x 16 x 32 with the half-tile path (N = 1408: a
-    // whole tile for the half column costs fc2 6 %)
+    // consumers, whose registers are tightest (qkv, N = 4224: 3 % padding, +2.1 %); 2 = 16 x 16 x 32 with an own form for the half column
+    // (N = 1408: a whole tile for it costs fc2 6 %): tall tiles (TALL below), 256 x 128 half tiles in the A3 instance
     constexpr bool M16 = M16K != 0, HT16 = M16K == 2;
+    // TALL: the half column (N % 256 == 128) of these instances is covered by tiles of 384 rows x 128 columns instead of 256 x 128 (the tile
+    // list: gemm_common.h tile_coords_tall).  A K-step of a tall tile is 384 A rows + 128 W rows = the 64 pieces of one step buffer (A in
+    // its first 48 KiB, W in the last 16), the 8 waves are 4 (M) x 2 (N) blocks of 96 x 64 (wave w: rows 96 (w % 4) .., columns 64 (w / 4) ..,
+    // so that an A slab is read by one early wave and its late twin): 6 + 4 fragments and 24 MFMAs per half K-step, three epilogue units
+    // per wave.  Same MFMA, same K order per output element as every other form: same bits.  A tall tile takes 0.79-0.90 of a whole tile's
+    // time where a half tile took 0.74-0.77 for two thirds of the work; same-box A/B against the half tiles at the ViT's launch shape, bit-
+    // identical: fc2 + statistics +2.7 ... +3.6 %, proj + statistics +1.0 ... +1.1 % (inside twice its spread; -1.2 % in the bench); the bench step
+    // -0.65 % (profiles/tall_tiles_ab.log, tall_tiles_timeline.log, tall_tiles_bench.json).
+    // Not the A3 instance: its A ring has 32-KiB slots (three of 48 KiB do not fit the LDS), so it keeps the 256 x 128 half tile.
+    constexpr bool TALL = HT16 && !A3;
+    constexpr int TALL_BM = 384;
+    constexpr int HT_WM = TALL ? TALL_BM / 4 : 64, HT_TM16 = HT_WM / 16;  // rows per wave of a tall / half tile (16 x 16 form)
     static_assert(!M16 || !F8, "16 x 16 form: bf16 instances");
     constexpr int BM = 256, BN = 256, NWM = 2, NWN = 4, NW = 8;
     constexpr int WM = BM / NWM, WN = BN / NWN, TM = WM / 32, TN = WN / 32;
@@ -53,7 +65,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     auto a_slot = [&](int st) { return smem + (A3 ? (st % 3) * (BM * 128) : (st & 1) * STEP); };
     auto w_slot = [&](int st) { return smem + (A3 ? 3 * (BM * 128) + (st & 1) * (BN * 128) : (st & 1) * STEP + BM * 128); };
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN, ntiles = tiles_m * tiles_n;
+    const bool tall_n = TALL && (g.N & 255) == 128;  // this launch has a half column, run as tall tiles
+    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN, ntiles = tall_n ? tall_ntiles(g.M, g.N) : tiles_m * tiles_n;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid / NWN, wn = wid % NWN;
@@ -76,11 +89,32 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)g.W, 0, 0x7fffffff, 0x00020000);
     unsigned po[PC];  // per-lane byte offsets of this wave's pieces (chunk-swizzled source): into A for waves 0-3, into W for waves 4-7
     const int pw = late ? wid - NW / 2 : wid;  // which 64-row slab of its operand the wave stages
+    // Tall tiles keep the rule and the DMA schedule of whole tiles (kstep below) with another split of the rows.  The late wave 4 + j stages
+    // rows 0..63 of A slab j (rows 96 j .. of the tile): its own A rows, which besides it only its early twin j reads, one barrier interval
+    // EARLIER — so it may overwrite them at the end of its own reads of (st, half 1), as it does with its W rows in a whole tile.  The early
+    // wave j stages what several late waves read: rows 64..95 of A slab j (pieces 0..3) and W rows 32 j .. 32 j + 31 (pieces 4..7); the
+    // early group only ever issues behind the barrier that ends the previous K-step's last reads of the buffer, whatever the rows.
+    // (First built with the half tile's schedule — every wave's 8 pieces in one burst, the late group's behind its barrier: both bursts
+    // fell into the same interval and a tall tile took 0.93 ... 0.98 of a whole tile's time, profiles/tall_tiles_timeline.log.)
+    bool src_a = !late;        // (wave-uniform) pieces 0..3 of the tile being staged come from A ...
+    bool src_a_hi = !late;     // ... and pieces 4..7
+    int d_lo = wid * (PC * 1024), d_hi = wid * (PC * 1024) + (PC / 2) * 1024;  // TALL instances: where pieces 0..3 / 4..7 land in the step buffer
     auto set_tile = [&](int t, int &m0, int &n0) {
-        int tm_i, tn_i;
-        tile_coords(g, tiles_m, tiles_n, tm_i, tn_i, t);
-        m0 = tm_i * BM;
-        n0 = tn_i * BN;
+        if (tall_n) {
+            if constexpr (TALL) tile_coords_tall(g, m0, n0, t);
+        } else {
+            int tm_i, tn_i;
+            tile_coords(g, tiles_m, tiles_n, tm_i, tn_i, t);
+            m0 = tm_i * BM;
+            n0 = tn_i * BN;
+        }
+        const bool tt = TALL && n0 + 128 >= g.N;  // a tall tile
+        src_a = !late || tt;
+        src_a_hi = tt ? late : !late;
+        if constexpr (TALL) {
+            d_lo = tt ? (pw * HT_WM + (late ? 0 : 64)) * 128 : wid * (PC * 1024);
+            d_hi = tt ? (late ? d_lo + (PC / 2) * 1024 : (TALL_BM + pw * 32) * 128) : d_lo + (PC / 2) * 1024;
+        }
         {
 #ifdef EILEV_PP4_PROBE_A0  /* timing probe only (WRONG results): every tile reads the A rows of tile row 0 — same data statistics, no fabric traffic for A */
             const uint64_t base = (uint64_t)(g.A);
@@ -93,9 +127,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
         }
 #pragma unroll
         for (int i = 0; i < PC; ++i) {
-            const int row = (pw * PC + i) * 8 + prow;
+            // the piece's first row in its operand (a multiple of 16 away from its row of the step buffer: same swizzle)
+            const int row = (!tt ? (pw * PC + i) * 8 : late ? pw * HT_WM + i * 8 : i < PC / 2 ? pw * HT_WM + 64 + i * 8 : pw * 32 + (i - PC / 2) * 8) + prow;
             const unsigned sw = (unsigned)((pslot ^ ((row >> 1) & 7)) << 4);
-            if (!late) {
+            if (i < PC / 2 ? src_a : src_a_hi) {
                 int gr = m0 + row;
                 gr = gr < g.M ? gr : g.M - 1;
                 po[i] = (unsigned)(gr - m0) * (unsigned)(g.lda * 2) + sw;
@@ -115,7 +150,20 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
 #endif
         constexpr int PCE = (EILEV_PP4_PROBE_SKIP & 4) ? 0 : (EILEV_PP4_PROBE_SKIP & 1) ? PC / 2 : PC;
         constexpr int PCL = (EILEV_PP4_PROBE_SKIP & 8) ? 0 : (EILEV_PP4_PROBE_SKIP & 2) ? PC / 2 : PC;
-        if (late) {
+        if constexpr (TALL) {  // whole and tall tiles: the two halves of a wave's pieces have their own source and their own LDS rows
+            char *sb2 = smem + (st & 1) * STEP;
+            auto issue4 = [&](int i0, bool from_a, char *dst) {
+                if (from_a) {
+#pragma unroll
+                    for (int i = 0; i < PC / 2; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void *)(dst + i * 1024), 16, po[i0 + i], st * 128, 0, 0);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < PC / 2; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void *)(dst + i * 1024), 16, po[i0 + i], st * 128, 0, 0);
+                }
+            };
+            if (part != 2) issue4(0, src_a, sb2 + d_lo);
+            if (part != 1) issue4(PC / 2, src_a_hi, sb2 + d_hi);
+        } else if (late) {
 #pragma unroll
             for (int i = 0; i < PCL; ++i)
                 if (part == 0 || (part == 1) == (i < PC / 2)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void *)(sd + i * 1024), 16, po[i], st * 128, 0, 0);
@@ -196,12 +244,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     };
     // Half-empty last column tile (N % 256 <= 128, e.g. N = 1408 = 5.5 x 256): only columns [0, 128) of the tile exist.
     // The 8 waves re-split the valid 256 x 128 region as 4 x 2 blocks of 64 x 64 (half the fragment reads and MFMAs per
-    // wave, same ping-pong schedule); waves 4..7 own W rows 128..255 of the tile and skip their W pieces.
-    const int hm = wm * 2 + (wn >> 1), hn = wn & 1;
+    // wave, same ping-pong schedule); waves 4..7 own W rows 128..255 of the tile and skip their W pieces.  TALL instances: the
+    // tile is 384 x 128 and the blocks are 96 x 64 (TALL above); the same two functions read and multiply them.
+    const int hm = TALL ? wid & 3 : wm * 2 + (wn >> 1), hn = TALL ? wid >> 2 : wn & 1;
     auto read_half_ht = [&](int st, int h) {
-        const char *sa = a_slot(st) + (hm * 64) * 128;
-        const char *sb = w_slot(st) + (hn * 64) * 128;
-        if constexpr (M16) {  // 64 x 64 per wave: 4 + 4 fragments of the one 32-wide k-slice
+        const char *sa = a_slot(st) + (hm * HT_WM) * 128;
+        const char *sb = (TALL ? a_slot(st) + TALL_BM * 128 : w_slot(st)) + (hn * 64) * 128;
+        if constexpr (M16) {  // 96 x 64 (tall) or 64 x 64 per wave: 4 + 6 or 4 + 4 fragments of the one 32-wide k-slice
             const int kc = h * 4 + g4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -209,9 +258,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
                 bfr[j >> 1][j & 1] = *reinterpret_cast<const bf16x8 *>(sb + row * 128 + swz(row, kc));
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < HT_TM16; ++i) {
                 const int row = i * 16 + l15;
-                af[0][i] = *reinterpret_cast<const bf16x8 *>(sa + row * 128 + swz(row, kc));
+                af[i >> 2][i & 3] = *reinterpret_cast<const bf16x8 *>(sa + row * 128 + swz(row, kc));
             }
             return;
         }
@@ -241,10 +290,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
                                                                                0, 0, 0, 0, 0, 0);
         } else if constexpr (M16) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < HT_TM16; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j >> 1][j & 1], af[0][i], acc16[i][j], 0, 0, 0);
+                    acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j >> 1][j & 1], af[i >> 2][i & 3], acc16[i][j], 0, 0, 0);
         } else {
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2)
@@ -280,9 +329,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     float ln_rs[LN == 1 ? (M16 ? TM16 : TM) : 1];  // LN == 1: rstd of the lane's row in each of its units (M16: 16-row blocks), fetched at the end of the K loop
     auto lean_epilogue = [&](int cm0, int cn0, auto res_c, auto ht_c) {
         constexpr bool RES = decltype(res_c)::value;
-        constexpr bool HTE = decltype(ht_c)::value;  // M16 only: the half tile's 64 x 64 block of this wave (rows 64 hm .., columns 64 hn ..)
-        constexpr int NU = HTE ? 2 : TM;              // units of 32 rows
-        const int roff = HTE ? hm * 64 : wm * WM, coff = HTE ? hn * 64 : wn * WN;
+        constexpr bool HTE = decltype(ht_c)::value;  // M16 only: this wave's block of the tall / half tile (rows HT_WM hm .., columns 64 hn ..)
+        constexpr int NU = HTE ? HT_WM / 32 : TM;     // units of 32 rows
+        const int roff = HTE ? hm * HT_WM : wm * WM, coff = HTE ? hn * 64 : wn * WN;
         if constexpr (M16K == 1) {
             if (cn0 + coff >= g.N) return;  // (wave-uniform) this wave's 64 columns do not exist: the half-valid last column tile run whole
         }
@@ -533,7 +582,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     if (t >= ntiles) return;
     set_tile(t, m0, n0);
     // half tile: only W rows 0..127 of the tile exist; the late waves 6 and 7 (rows 128..255) have nothing to stage
-    auto w_piece_mine = [&](int n0_) { return !(n0_ + 128 >= g.N && !(g.dbg & DBG_GEMM_NO_HALF_TILES)) || wid < NW / 2 + 2; };
+    // (a tall tile: every wave has 8 pieces)
+    auto w_piece_mine = [&](int n0_) { return TALL || !(n0_ + 128 >= g.N && !(g.dbg & DBG_GEMM_NO_HALF_TILES)) || wid < NW / 2 + 2; };
     stage_step(0, w_piece_mine(n0));
     bool pre1 = ns > 1 && (A3 || !(g.dbg & DBG_GEMM_PP4_NO_PRESTAGE));  // step 1 of the coming tile is already staged (prologue / previous tile's tail)
     if (pre1) stage_step(1, w_piece_mine(n0));
@@ -549,7 +599,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
     auto ln_fetch = [&](int m0_, int n0_) {
         if constexpr (LN == 1 && M16) {  // the lane's rows 16 i + l15 and columns 16 j + l15 (the operand layout of the 16 x 16 MFMA)
             const bool ht = HT16 && n0_ + 128 >= g.N;
-            const int mb = m0_ + (ht ? hm * 64 : wm * WM) + l15, nb = n0_ + (ht ? hn * 64 : wn * WN) + l15;
+            const int mb = m0_ + (ht ? hm * HT_WM : wm * WM) + l15, nb = n0_ + (ht ? hn * 64 : wn * WN) + l15;
             const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)g.ln_rows, 0, g.M * 8, 0x00020000);
             const __amdgpu_buffer_rsrc_t rcs = __builtin_amdgcn_make_buffer_rsrc((void *)g.ln_csum, 0, g.N * 4, 0x00020000);
 #pragma unroll
@@ -673,7 +723,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
         auto kstep = [&](int st, auto first_c, auto ht_c) {
             constexpr bool FIRST = decltype(first_c)::value;
             constexpr bool HT = decltype(ht_c)::value;
-            const bool w_mine = !HT || wid < NW / 2 + 2;
+            const bool w_mine = !HT || TALL || wid < NW / 2 + 2;
             ITR(0);
             if constexpr (HT) read_half_ht(st, 0); else read_half(st, 0);
 #if EILEV_PP4_DEEP
@@ -693,7 +743,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
 #ifndef EILEV_PP4_SPLIT_QKV
 #define EILEV_PP4_SPLIT_QKV 0
 #endif
-            constexpr bool SPLIT_OK = !HT && (EILEV_PP4_SPLIT_QKV || !(LN == 1 && EPI == 0));
+            constexpr bool SPLIT_OK = (!HT || TALL) && (EILEV_PP4_SPLIT_QKV || !(LN == 1 && EPI == 0));  // (tall tiles: the whole tile's schedule)
             constexpr bool SPLIT_E = (EILEV_PP4_SPLIT & 1) && SPLIT_OK, SPLIT_L = (EILEV_PP4_SPLIT & 2) && SPLIT_OK;
             if (!late) {
                 if constexpr (A3) {  // steps 0 and 1 came with the tile's head; A of step st + 2 goes into the slot both groups left at the last barrier
@@ -721,7 +771,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
                 PP_WAIT_VM0();
                 // full tile: the W rows this wave stages are read by itself (done: lgkmcnt(0) above) and by its early twin (done one
                 // barrier ago) only.  Half tile: the reads are re-split 4 x 2, two late waves share W rows -> issue after the barrier.
-                if constexpr (!HT) if (st + 2 < ns) stage_step(st + 2, w_mine, SPLIT_L ? 1 : 0);
+                // Tall tile: rows 0..63 of the A slab that this wave and its early twin read (set_tile) — the same argument.
+                if constexpr (!HT || TALL) if (st + 2 < ns) stage_step(st + 2, w_mine, SPLIT_L ? 1 : 0);
             } else if (A3) {
                 if (SPLIT_E && st + 2 < ns) stage_step(st + 2, w_mine, 2);
             } else if (SPLIT_E && st + 1 < ns && !(FIRST && pre1)) stage_step(st + 1, w_mine, 2);
@@ -729,7 +780,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
             PP_BARRIER();
             ITR(6);
             if constexpr (HT) {
-                if (late && st + 2 < ns) stage_step(st + 2, w_mine);
+                if constexpr (!TALL) if (late && st + 2 < ns) stage_step(st + 2, w_mine);
                 mma_half_ht();
             } else mma_half();
             __builtin_amdgcn_sched_barrier(0);
@@ -770,7 +821,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp4_kernel(const GemmArgs g) {
             const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)g.ln_rows, 0, g.M * 8, 0x00020000);
             if constexpr (M16) {
 #pragma unroll
-                for (int i = 0; i < TM16; ++i) ln_rs[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, (m0 + ((HT16 && half_tile) ? hm * 64 : wm * WM) + i * 16 + l15) * 8, 0, 0));
+                for (int i = 0; i < TM16; ++i) ln_rs[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, (m0 + ((HT16 && half_tile) ? hm * HT_WM : wm * WM) + i * 16 + l15) * 8, 0, 0));
             } else {
 #pragma unroll
             for (int u = 0; u < TM; ++u) ln_rs[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, (m0 + wm * WM + u * 32 + l31) * 8, 0, 0));

@@ -2,9 +2,11 @@
 """GPU probe (round 6): the TIMELINE of a persistent-GEMM launch — who runs which tile when.
 
     python tools/gemm_timeline.py [fc2_st|proj_st|fc2_n1536|...] [rows]
+    TIMELINE_LIB=<probe build of another commit> TIMELINE_TILES=half python tools/gemm_timeline.py ...   (a library from before the tall tiles)
 
 Same stamps as tools/gemm_trace.py (s_memrealtime, 100 MHz, one clock for the chip), read per workgroup instead of averaged:
-  * duration of whole tiles and of half tiles (the last column tile of N = 1408), from the tile coordinates of the static stride;
+  * duration of whole tiles and of the half column's tiles (N = 1408: tall tiles of 384 x 128 — gemm_common.h tile_coords_tall — on the
+    16 x 16 instances without the A ring, half tiles of 256 x 128 elsewhere), from the tile coordinates of the static stride;
   * when each workgroup finishes its last tile (the launch ends with the slowest): balance;
   * per round of the static stride, the spread of the tile START times inside an XCD (32 workgroups that share an L2): drift —
     tiles that share an A row panel only meet in the L2 if they walk K within a few K-steps of each other."""
@@ -18,9 +20,13 @@ import torch
 
 from eilev_amd import abi
 
-abi.use_probes()
-lib = abi.load_hip()
-raw = C.CDLL(abi.HIP_LIB_PATH)
+if os.environ.get("TIMELINE_LIB"):
+    lib = abi.load_library(os.path.abspath(os.environ["TIMELINE_LIB"]))
+    raw = C.CDLL(os.path.abspath(os.environ["TIMELINE_LIB"]))
+else:
+    abi.use_probes()
+    lib = abi.load_hip()
+    raw = C.CDLL(abi.HIP_LIB_PATH)
 P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
 st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
 SHAPES = {"fc2": (1408, 6144, True), "proj": (1408, 1408, True), "proj_st": (1408, 1408, True), "fc2_st": (1408, 6144, True),
@@ -53,14 +59,28 @@ ms = e0.elapsed_time(e1)
 t = buf.cpu().numpy().reshape(WG, 2, TILES, 8).astype(np.float64)[:, 0] * 0.01  # early waves, microseconds
 print(f"{name}: M={m} N={n} K={k}  {ms * 1e3:.0f} us  {2 * m * n * k / ms / 1e9:.0f} TFLOP/s (traced launch: the stamps cost ~10 %)")
 tiles_m, tiles_n = (m + 255) // 256, (n + 255) // 256
-ntiles = tiles_m * tiles_n
 half_col = (n % 256) != 0 and (n % 256) <= 128
+# tall tiles: the 16 x 16 instances (N % 128 == 0) except the three-deep A ring (plain launches with K >= 5120: gemm.hip a3_takes)
+tall = n % 256 == 128 and not (not name.endswith("_st") and k >= 5120) and os.environ.get("TIMELINE_TILES", "tall") != "half"
+ntiles = tiles_m * (n // 256) + (m + 383) // 384 if tall else tiles_m * tiles_n
 gm = 4 if tiles_n <= 8 else 8
+HALF_NAME = "tall" if tall else "half"
 
 
-def coords(tt):  # gemm_common.h tile_coords
+def coords(tt):  # gemm_common.h tile_coords / tile_coords_tall: (row tile or, in the half column, tall-tile index; column tile)
     xcd, q, rr = tt & 7, ntiles >> 3, ntiles & 7
     o_ = (xcd * (q + 1) if xcd < rr else rr * (q + 1) + (xcd - rr) * q) + (tt >> 3)
+    if tall:
+        tn_full = n // 256
+        gfull = 4 * tn_full + 3
+        sup, rem = divmod(o_, 3 * gfull - 1)
+        gi = 2 if rem >= 2 * gfull else 1 if rem >= gfull else 0
+        group, inn = sup * 3 + gi, rem - gi * gfull
+        first = group * 4
+        gsz = min(tiles_m - first, 4)
+        if inn < gsz * tn_full:
+            return first + inn % gsz, inn // gsz
+        return (8 * group + 2) // 3 + inn - gsz * tn_full, tiles_n - 1
     width = gm * tiles_n
     group = o_ // width
     first = group * gm
@@ -86,7 +106,7 @@ for wg in range(WG):
         rounds.setdefault(i, []).append((wg & 7, start[wg, i], end[wg, i]))
 pf = lambda x: f"n={len(x)} mean {np.mean(x):.1f} p5 {np.percentile(x, 5):.1f} p50 {np.percentile(x, 50):.1f} p95 {np.percentile(x, 95):.1f}" if len(x) else "n=0"
 print(f"  whole tiles (us): {pf(dur_full)}")
-print(f"  half  tiles (us): {pf(dur_half)}" + (f"   -> half / whole = {np.mean(dur_half) / np.mean(dur_full):.2f}" if dur_half else ""))
+print(f"  {HALF_NAME}  tiles (us): {pf(dur_half)}" + (f"   -> {HALF_NAME} / whole = {np.mean(dur_half) / np.mean(dur_full):.2f}" if dur_half else ""))
 last_end = np.array([end[wg][valid[wg]].max() if valid[wg].any() else 0.0 for wg in range(WG)])
 ntile_wg = valid.sum(1)
 print(f"  workgroup finish times (us): min {last_end.min():.0f}  p25 {np.percentile(last_end, 25):.0f}  p50 {np.percentile(last_end, 50):.0f}  "
