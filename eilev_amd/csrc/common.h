@@ -360,16 +360,23 @@ __host__ __device__ static inline int64_t frag32_index(int row, int col) { retur
 // 1000 gemm_nt_kernel / 2000 gemm_glds_kernel + 10 * tile (1 256 x 256, 2 256 x 128 two stages, 3 256 x 128 one stage, 4 128 x 128,
 // 5 64 x 128) + epi; 3000 + slices: split-K; 4000 + 100 * LN + 10 * instance (0 32 x 32 MFMAs, 1 / 2 the 16 x 16 forms M16K = 1 / 2, 3 A3,
 // 4 fp8 MFMA) + epi: gemm_pp4_kernel; 5000 + epi: gemm_w6_kernel.  Bits above: the launch was cut into row chunks / its fp8 weights expanded.
+// The M <= 32 family (gemm_skinny.h): 6000 gemm_skinny_kernel; 6100 + 10 MB + PRE gemm_skinny_dma_kernel; 6200 + 10 MB + NB gemm_skinny_nb_kernel;
+// 6300 + KS gemm_rows32_kernel; 6400 + 10 MB + PRE gemm_skinny_w8_kernel.  Bits: K split over gridDim.y (GEMM_FORM_KS records the slice count),
+// the reduce that also wrote the LayerNorm rows, the stream layout (GemmArgs::Wp) actually read.
 // A plain global on purpose: GemmArgs::dbg would move the launch off the product's route.  The product library has neither.
 #ifdef EILEV_PROBES
 extern int g_gemm_form;
 #define GEMM_FORM(code) (g_gemm_form = (g_gemm_form & ~0xffff) | (code))
 #define GEMM_FORM_BIT(bit) (g_gemm_form |= (bit))
+extern int g_gemm_ks;
+#define GEMM_FORM_KS(n) (g_gemm_ks = (n))
 #else
 #define GEMM_FORM(code) ((void)0)
 #define GEMM_FORM_BIT(bit) ((void)0)
+#define GEMM_FORM_KS(n) ((void)0)
 #endif
-enum : int { GEMM_FORM_ROW_CHUNKS = 1 << 16, GEMM_FORM_W8_EXPANDED = 1 << 17 };
+enum : int { GEMM_FORM_ROW_CHUNKS = 1 << 16, GEMM_FORM_W8_EXPANDED = 1 << 17, GEMM_FORM_SPLIT_K = 1 << 18, GEMM_FORM_REDUCE_LN = 1 << 19,
+             GEMM_FORM_STREAM_LAYOUT = 1 << 20 };
 
 int launch_gemm(const GemmArgs &g, int prof_kind, hipStream_t s);
 bool gemm_rows32_takes(const GemmArgs &g);  // would launch_gemm run g on gemm_rows32_kernel (the one kernel of the row-block layout)?

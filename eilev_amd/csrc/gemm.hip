@@ -29,6 +29,7 @@ int g_gemm_debug = 0;  // probe-only switches (tools/gemm_probe.py): GemmArgs::d
 extern "C" int eilev_debug_gemm_flags(int f) { g_gemm_debug = f; return 0; }
 extern "C" int eilev_debug_grid_cus(int n) { g_eilev_grid_cus = n; return 0; }
 int g_gemm_form = 0;   // common.h GEMM_FORM: what eilev_debug_gemm (end of this file) reports
+int g_gemm_ks = 0;     // common.h GEMM_FORM_KS: the K slices of the last M <= 32 launch (eilev_debug_gemm_skinny)
 #endif
 #ifdef EILEV_PROBES
 unsigned long long *g_gemm_trace = nullptr;  // probe-only: see GemmArgs::trace
@@ -165,7 +166,10 @@ int skinny_reduce(const GemmArgs &g, const SkinnyArgs &a, hipStream_t s, bool *l
         (!g.resid || (g.ldr & 7) == 0)) {
         const int rc = launch_reduce_ln(a.part, a.ks, a.mr, g.M, g.N, g.wscale, g.bias, g.resid, g.ldr, reinterpret_cast<bf16 *>(g.C), g.ldc,
                                         g.ln_gamma, g.ln_beta, g.ln_out, g.ln_eps, s, g.ln_frag);
-        if (rc == EILEV_OK) *ln_done = true;
+        if (rc == EILEV_OK) {
+            *ln_done = true;
+            GEMM_FORM_BIT(GEMM_FORM_REDUCE_LN);
+        }
         return rc;
     }
     if (g.ln_frag) return EILEV_E_UNSUPPORTED;  // (the row-block LayerNorm rows exist in the fused reduce only)
@@ -197,7 +201,10 @@ int launch_skinny(const GemmArgs &g, hipStream_t s, bool *ln_done) {
     const bool dma_ok = skinny_dma_ok(g), m32 = g.M > 16;
     const dim3 grid(nb, ks);
     int rc;
+    GEMM_FORM_KS(ks);
+    if (ks > 1) GEMM_FORM_BIT(GEMM_FORM_SPLIT_K);
     if (g.W8) {
+        GEMM_FORM(6400 + (m32 ? 20 : 10) + (pre ? 1 : 0));
         if (m32) rc = pre ? eilev_launch<gemm_skinny_w8_kernel<2, true>>(grid, dim3(256), 0, s, a) : eilev_launch<gemm_skinny_w8_kernel<2, false>>(grid, dim3(256), 0, s, a);
         else rc = pre ? eilev_launch<gemm_skinny_w8_kernel<1, true>>(grid, dim3(256), 0, s, a) : eilev_launch<gemm_skinny_w8_kernel<1, false>>(grid, dim3(256), 0, s, a);
     } else if (r32) {
@@ -205,20 +212,27 @@ int launch_skinny(const GemmArgs &g, hipStream_t s, bool *ln_done) {
         // workgroups row by row (with a K split the grid is still one workgroup per CU).  The stream layout has no row stride, and a
         // first-fit plan's grid may differ from the one the copy was dealt for.
         if (a.g.Wp && (g.ldw != g.K || (g.dbg & (DBG_GEMM_NO_STREAM_LAYOUT | DBG_GEMM_ROWS32_FIRST_FIT)))) a.g.Wp = nullptr;
+        if (a.g.Wp) GEMM_FORM_BIT(GEMM_FORM_STREAM_LAYOUT);
+        GEMM_FORM(6300 + ks32);
         const dim3 g32(r32_grid, ks);
         if (ks32 == 10) rc = eilev_launch<gemm_rows32_kernel<2, 10, 3>>(g32, dim3(512), 0, s, a);
         else if (ks32 == 8) rc = eilev_launch<gemm_rows32_kernel<2, 8, 3>>(g32, dim3(512), 0, s, a);
         else rc = eilev_launch<gemm_rows32_kernel<2, 5, 4>>(g32, dim3(512), 0, s, a);
     } else if (dma_ok && pre && nbsel > 1) {
+        GEMM_FORM(6200 + (m32 ? 20 : 10) + (m32 ? nbsel : (nbsel == 4 ? 4 : 2)));
         if (m32 && nbsel == 8) rc = launch_skinny_nb<2, 8>(a, nb, s);
         else if (m32 && nbsel == 4) rc = launch_skinny_nb<2, 4>(a, nb, s);
         else if (m32) rc = launch_skinny_nb<2, 2>(a, nb, s);
         else if (nbsel == 4) rc = launch_skinny_nb<1, 4>(a, nb, s);
         else rc = launch_skinny_nb<1, 2>(a, nb, s);
     } else if (dma_ok) {
+        GEMM_FORM(6100 + (m32 ? 20 : 10) + (pre ? 1 : 0));
         if (m32) rc = pre ? eilev_launch<gemm_skinny_dma_kernel<2, true>>(grid, dim3(256), 0, s, a) : eilev_launch<gemm_skinny_dma_kernel<2, false>>(grid, dim3(256), 0, s, a);
         else rc = pre ? eilev_launch<gemm_skinny_dma_kernel<1, true>>(grid, dim3(256), 0, s, a) : eilev_launch<gemm_skinny_dma_kernel<1, false>>(grid, dim3(256), 0, s, a);
-    } else rc = eilev_launch<gemm_skinny_kernel>(grid, dim3(256), 0, s, a);
+    } else {
+        GEMM_FORM(6000);
+        rc = eilev_launch<gemm_skinny_kernel>(grid, dim3(256), 0, s, a);
+    }
     if (rc != EILEV_OK || ks == 1) return rc;
     return skinny_reduce(g, a, s, ln_done);
 }
@@ -281,7 +295,7 @@ bool w6_ok(const GemmArgs &g) {
 // The old rule (w6 below 1024 tiles) stays for N that is not a whole number of 256-column tiles.
 bool w6_pick(const GemmArgs &g) {
     const int64_t tm256 = ceil_div64(g.M, 256), tiles256 = tm256 * ceil_div64(g.N, 256);
-    const int n_cu_q = skinny_n_cu() / 8 * 8;
+    const int n_cu_q = eilev_num_cu() / 8 * 8;  // (the device's CUs in both builds: the probe build's grid override moves the M <= 32 family only)
     auto fill = [&](int64_t t) { return (double)t / (double)(ceil_div64(t, n_cu_q) * n_cu_q); };
     return g.N % 256 == 0 ? 1.06 * fill(tiles256) < fill(tm256 * ceil_div64(g.N, 128)) : tiles256 < 1024;
 }
@@ -372,6 +386,9 @@ extern "C" int eilev_stream_layout_pack(const void *w, int64_t n, int64_t k, voi
 
 int launch_gemm(const GemmArgs &g, int prof_kind, hipStream_t s) {
     bool ln_done = false;
+    // ln_out that neither the fused reduce nor a LayerNorm launch (norm.hip: cols % 8 == 0, cols <= 4096, ldx % 8 == 0) can write is refused
+    // HERE: refused after the GEMM, the launch had written C (and the split-K planes) and then returned an error
+    if (g.ln_out && g.M > 0 && (g.out_f32 || g.patch_group || (g.N & 7) || g.N > 4096 || (g.ldc & 7))) return EILEV_E_UNSUPPORTED;
     const int rc = launch_gemm_core(g, prof_kind, s, &ln_done);
     if (rc != EILEV_OK || !g.ln_out || ln_done || g.M <= 0) return rc;
     if (g.out_f32 || g.patch_group) return EILEV_E_UNSUPPORTED;
@@ -428,8 +445,7 @@ struct EilevDebugGemmArgs {
     float ln_eps;
     int32_t pad1;
 };
-extern "C" int eilev_debug_gemm(const EilevDebugGemmArgs *args, size_t struct_bytes, int *form, void *stream) {
-    if (!args || struct_bytes != sizeof(EilevDebugGemmArgs)) return EILEV_E_BADARG;
+static GemmArgs debug_gemm_args(const EilevDebugGemmArgs *args) {
     GemmArgs g = {};
     g.A = (const bf16 *)args->A; g.lda = args->lda; g.W = (const bf16 *)args->W; g.ldw = args->ldw;
     g.bias = (const bf16 *)args->bias; g.resid = (const bf16 *)args->resid; g.ldr = args->ldr; g.C = args->C; g.ldc = args->ldc;
@@ -440,9 +456,34 @@ extern "C" int eilev_debug_gemm(const EilevDebugGemmArgs *args, size_t struct_by
     g.A8 = (const uint8_t *)args->A8; g.ascale = args->ascale; g.ln_rows = args->ln_rows; g.ln_csum = args->ln_csum;
     g.stat_out = args->stat_out; g.stat_ld = args->stat_ld;
     g.ln_gamma = (const bf16 *)args->ln_gamma; g.ln_beta = (const bf16 *)args->ln_beta; g.ln_out = (bf16 *)args->ln_out; g.ln_eps = args->ln_eps;
+    return g;
+}
+extern "C" int eilev_debug_gemm(const EilevDebugGemmArgs *args, size_t struct_bytes, int *form, void *stream) {
+    if (!args || struct_bytes != sizeof(EilevDebugGemmArgs)) return EILEV_E_BADARG;
+    const GemmArgs g = debug_gemm_args(args);
     g_gemm_form = 0;
     const int rc = launch_gemm(g, -1, (hipStream_t)stream);
     if (form) *form = g_gemm_form;
+    return rc;
+}
+// The same for the M <= 32 family (tests/test_hip_gemm_skinny.py): the struct above followed by what only a decode launch passes — the
+// split-K scratch, the stream-layout copy of W and the three row-block layout switches.  *ks receives the K slices of the launch (0: none).
+struct EilevDebugSkinnyArgs {
+    EilevDebugGemmArgs g;
+    void *scratch; uint64_t scratch_bytes;
+    const void *Wp;
+    int32_t a_frag, c_frag, ln_frag, pad2;
+};
+extern "C" int eilev_debug_gemm_skinny(const EilevDebugSkinnyArgs *args, size_t struct_bytes, int *form, int *ks, void *stream) {
+    if (!args || struct_bytes != sizeof(EilevDebugSkinnyArgs)) return EILEV_E_BADARG;
+    GemmArgs g = debug_gemm_args(&args->g);
+    g.scratch = (float *)args->scratch; g.scratch_bytes = (size_t)args->scratch_bytes; g.Wp = (const bf16 *)args->Wp;
+    g.a_frag = args->a_frag; g.c_frag = args->c_frag; g.ln_frag = args->ln_frag;
+    g_gemm_form = 0;
+    g_gemm_ks = 0;
+    const int rc = launch_gemm(g, -1, (hipStream_t)stream);
+    if (form) *form = g_gemm_form;
+    if (ks) *ks = g_gemm_ks;
     return rc;
 }
 #endif

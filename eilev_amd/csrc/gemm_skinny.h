@@ -489,7 +489,14 @@ __global__ __launch_bounds__(512) void gemm_rows32_kernel(const SkinnyArgs a) {
     }
 }
 
+// (probe build: the grid override of eilev_debug_grid_cus applies, so that the ring, the tail and the uneven row deal of gemm_rows32_kernel are
+// reached with a few hundred weight rows; eilev_stream_layout_pack and gemm_rows32_takes use the same function, so a packed copy and the decode
+// step's layout choice stay consistent with the launch.  The wide family does not call it: w6_pick reads eilev_num_cu().)
+#ifdef EILEV_PROBES
+static int skinny_n_cu() { return eilev_grid_cus(); }
+#else
 static int skinny_n_cu() { return eilev_num_cu(); }
+#endif
 
 // Shape of a gemm_rows32_kernel launch, a function of (N, K, CUs) alone — the stream layout of a weight matrix is packed for it.
 // K split: the 8-wave K slice must be 5 or 10 k-steps of 32 (8: K = 2048, flan-t5, round 5); more splits while the matrix has fewer 16-row
