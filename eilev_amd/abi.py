@@ -690,11 +690,15 @@ def load_t5beam() -> C.CDLL:
 # ---- the shared-prefix companion library (include/eilev_prefix.h): rows of new positions that continue one cached prefix, stored once.
 # Like the flan-t5 beam library it carries its own copy of the core library's code and shares no state with it. ----
 PREFIX_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_prefix.so")
-PREFIX_ABI_VERSION = 1
+PREFIX_ABI_VERSION = 2
 PREFIX_MAX_ROWS = 4096
 PREFIX_MAX_NEW = 2048
 PREFIX_MAX_STACKED = 65536
-PREFIX_EXPORTS = ["eilev_prefix_abi_version", "eilev_prefix_attention", "eilev_prefix_extend", "eilev_prefix_workspace_bytes"]
+PREFIX_DECODE_PROMPT_KEYS = 128  # key ranges of the shared-prompt decode attention: the prompt's ...
+PREFIX_DECODE_GEN_KEYS = 128     # ... and the generated keys'
+PREFIX_DECODE_MAX_ROWS = 32
+PREFIX_EXPORTS = ["eilev_prefix_abi_version", "eilev_prefix_attention", "eilev_prefix_decode_attention", "eilev_prefix_decode_step",
+                  "eilev_prefix_decode_workspace_bytes", "eilev_prefix_extend", "eilev_prefix_workspace_bytes"]
 
 
 def prefix_supported(dims) -> bool:
@@ -709,9 +713,18 @@ def load_prefix() -> C.CDLL:
         sig("eilev_prefix_attention", _i32, vp, _i64, vp, _i64, vp, _i64, vp, vp, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, vp, vp)
         sig("eilev_prefix_workspace_bytes", _sz, DP, _i64, _i64)
         sig("eilev_prefix_extend", _i32, DP, C.POINTER(OptWeights), vp, _i64, _i64, vp, _i64, vp, _i64, vp, vp, vp, _sz, vp)
+        sig("eilev_prefix_decode_attention", _i32, vp, _i64, vp, vp, _i64, _i64, vp, vp, vp, vp, _i64, vp, _i64, _i64, _i64, _i64, vp, vp, _sz, vp)
+        sig("eilev_prefix_decode_workspace_bytes", _sz, DP, _i64, _i64, _i64)
+        sig("eilev_prefix_decode_step", _i32, DP, C.POINTER(OptWeights), vp, vp, vp, vp, _i64, _i64, _i64, vp, vp, _i64, vp, vp, vp, _sz, vp)
         return sig("eilev_prefix_abi_version", _i32)
 
     return _load_companion(PREFIX_LIB_PATH, PREFIX_ABI_VERSION, declare)
+
+
+def prefix_decode_part_bytes(rows: int, heads: int, hd: int, seq_len: int, gen_capacity: int) -> int:
+    """Bytes of `part` for eilev_prefix_decode_attention (include/eilev_prefix.h): one record of hd + 2 floats per (row, head, key range)."""
+    ns = -(-seq_len // PREFIX_DECODE_PROMPT_KEYS) + -(-gen_capacity // PREFIX_DECODE_GEN_KEYS)
+    return 4 * rows * heads * ns * (hd + 2)
 
 
 # ---- the fp8 KV-cache companion library (include/eilev_kv8.h): the OPT decode step over a cache of e4m3 bytes with one power-of-two scale

@@ -1,5 +1,6 @@
 // attn_decode.hip — single-query attention of a decode step against the KV cache: the flash-decoding split kernel and its merge, the
 // one-pass and 128-key-range kernels of small batches, the per-head loop of larger ones, and their launchers (common.h DecodeAttnArgs).
+#include "attn_tile64.h"
 #include "common.h"
 
 namespace {
@@ -297,12 +298,17 @@ __global__ __launch_bounds__(1024) void attn_decode1_kernel(const bf16 *__restri
 // seq_len in the prompt cache of sample b / beams, key seq_len + g in generation-cache row anc[g][b], the new token to this row's own slot —
 // with this kernel's 128-key ranges and up-front loads: 5 rows x 32 heads x 8 ranges = 1280 workgroups where the 256-key split kernel ran 640
 // of twice the length (15.3 us per block for 5 rows).
-template <int NCH, int VK, bool BEAM = false, int KEYS = 128>
+// WIN (the generated keys of the shared-prompt form, launch_attn_decode_shared): the ranges cover the key window that starts at seq_len —
+// range sp = keys [seq_len + sp * KEYS, ..) — and their records are nos. rec0 + sp of the nrec that a (row, head) has; the prompt keys
+// belong to attn_shared_prompt_kernel.
+template <int NCH, int VK, bool BEAM = false, int KEYS = 128, bool WIN = false>
 __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16 *__restrict__ qkv, bf16 *__restrict__ kc, bf16 *__restrict__ vc,
                                                                float *__restrict__ part, const int32_t *__restrict__ attn_mask,
                                                                const int32_t *__restrict__ state, int seq_len, int cap, int heads, int64_t ldq,
                                                                bf16 *__restrict__ kg_ = nullptr, bf16 *__restrict__ vg_ = nullptr,
-                                                               const int32_t *__restrict__ anc = nullptr, int beams = 1, int cap_g = 0, int rows = 0) {
+                                                               const int32_t *__restrict__ anc = nullptr, int beams = 1, int cap_g = 0, int rows = 0,
+                                                               int rec0 = 0, int nrec = 0) {
+    static_assert(BEAM || !WIN, "the key window is the generated keys of the beam form");
     using R = DecodeRange<NCH, VK, 256, KEYS>;
     constexpr int hd = R::hd;
     __shared__ __attribute__((aligned(16))) float qs[128];
@@ -310,12 +316,12 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16 *__res
     __shared__ float wred[8];
     __shared__ float red[R::RED];
     const int tid = threadIdx.x, c = tid % NCH;
-    const int h = blockIdx.x, b = blockIdx.y, sp = blockIdx.z, nsplit = gridDim.z, d = heads * hd;
+    const int h = blockIdx.x, b = blockIdx.y, sp = blockIdx.z, nsplit = WIN ? nrec : gridDim.z, d = heads * hd;
     const int kv_total = BEAM ? min(seq_len + cap_g, seq_len + state[0]) : min(cap, seq_len + state[0]);
     // (beam form: a caller that passes a step count of 0, or more than the generation cache holds, must not make this row write outside its slots)
     const int slot_new = BEAM && (kv_total - 1 < seq_len || state[0] > cap_g) ? -1 : kv_total - 1;
-    const int k0 = sp * KEYS, k1 = min(kv_total, k0 + KEYS);
-    float *po = part + (((int64_t)b * heads + h) * nsplit + sp) * (hd + 2);
+    const int k0 = (WIN ? seq_len : 0) + sp * KEYS, k1 = min(kv_total, k0 + KEYS);
+    float *po = part + (((int64_t)b * heads + h) * nsplit + (WIN ? rec0 : 0) + sp) * (hd + 2);
     if (k0 >= kv_total) {  // nothing in this split yet
         if (tid == 0) {
             po[0] = -1e30f;
@@ -565,6 +571,72 @@ __global__ __launch_bounds__(256) void attn_cross_shared_kernel(const bf16 *__re
     }
 }
 
+// ---- OPT beam search and generate(context=): the PROMPT keys of a sample, read once for its `beams` rows (DecodeAttnArgs.shared_prompt) ----------
+// Grid (heads, samples, ranges of 64 TILES prompt keys).  The sample's rows are the queries of attn_tile64.h's 64 x 64 tile, stacked along M as
+// prefix_attn_kernel stacks its rows: query slot wave * 16 + (lane & 15) is live below `beams` (rows <= 32: waves 2 and 3 only help staging).
+// A tile's K and V come from HBM once into LDS; S^T = K Q^T and O^T = V^T P^T run on the 16x16x32 MFMA with the tile's arithmetic — no
+// scale (q is pre-scaled), fp32 scores, P rounded to bf16 for the product, the row sum from the unrounded P.  Each live query leaves its
+// un-normalised (max, sum, o[hd]) as record no. `range` of the nsplit that a (row, head) has (layout of attn_decode_part_bytes); the tile's
+// scores are base-2, the record's maximum is the natural-log one attn_decode_merge_kernel takes.  A range in which a row sees nothing leaves
+// (-1e30, 0).  Key j is visible iff j < seq_len and attn_mask[sample][j] != 0 (null: every key); slots at or beyond seq_len are never
+// loaded; a masked key's K may hold anything (its score is dropped) and its V is zeroed in LDS, so 0 * NaN never reaches a sum.
+template <int DP, int TILES>
+__global__ __launch_bounds__(256) void attn_shared_prompt_kernel(const bf16 *__restrict__ qkv, int64_t ldq, const bf16 *__restrict__ kc,
+                                                                 const bf16 *__restrict__ vc, float *__restrict__ part,
+                                                                 const int32_t *__restrict__ attn_mask, int beams, int seq_len, int cap, int heads,
+                                                                 int hd, int nsplit) {
+    using Tile = AttnTile64<DP>;
+    __shared__ __attribute__((aligned(16))) char ks_[Tile::KS_BYTES];
+    __shared__ __attribute__((aligned(16))) char vt_[Tile::VT_BYTES];
+    __shared__ int vis_[64];  // the tile's key is visible
+    const int tid = threadIdx.x, wid = tid >> 6, l15 = tid & 15, lg = (tid & 63) >> 4;
+    const int h = blockIdx.x, smp = blockIdx.y, sp = blockIdx.z;
+    const int r0 = sp * 64 * TILES, r1 = min(seq_len, r0 + 64 * TILES);
+    const int slot = wid * 16 + l15;
+    const bool live = slot < beams, wave_live = wid * 16 < beams;
+    const int row = smp * beams + (live ? slot : 0);
+    Tile t;
+    t.init(live, qkv + (int64_t)row * ldq + h * hd, hd);
+    const bf16 *kb = kc + ((int64_t)smp * heads + h) * cap * hd, *vb = vc + ((int64_t)smp * heads + h) * cap * hd;
+    const int32_t *mrow = attn_mask ? attn_mask + (int64_t)smp * seq_len : nullptr;
+    for (int k0 = r0; k0 < r1; k0 += 64) {
+        __syncthreads();  // everyone is done reading the previous tile
+        Tile::stage(ks_, vt_, kb, hd, vb, hd, k0, r1, hd);
+        bool hidden = false;
+        if (tid < 64) {
+            const int j = k0 + tid;
+            const bool v = j < r1 && (!mrow || mrow[j] != 0);
+            vis_[tid] = v;
+            hidden = j < r1 && !v;
+        }
+        if (__syncthreads_or(hidden)) {  // (uniform) some staged key is masked: its V column out of the product
+            for (int id = tid; id < 64 * DP; id += 256) {
+                const int key = id & 63, dd = id >> 6;
+                if (!vis_[key]) *reinterpret_cast<bf16 *>(vt_ + dd * Tile::VSTR + key * 2) = (bf16)0.0f;
+            }
+            __syncthreads();
+        }
+        if (wave_live)
+            t.step(
+                ks_, vt_, [&](int kl) { return vis_[kl] != 0; }, [](int, float s) { return s * 1.44269504088896340736f; }, [](int, float p) { return p; });
+    }
+    if (live) {  // o[dt][r] = O[q = l15][d = dt * 16 + lg * 4 + r]
+        float *po = part + (((int64_t)row * heads + h) * nsplit + sp) * (hd + 2);
+        if (lg == 0) {
+            po[0] = t.l_run > 0.0f ? t.m_run * 0.69314718055994530942f : -1e30f;
+            po[1] = t.l_run;
+        }
+#pragma unroll
+        for (int dt = 0; dt < Tile::DT; ++dt) {
+            const int d0 = dt * 16 + lg * 4;
+            if (d0 < hd) {  // (records are 8-byte aligned: hd + 2 is even)
+                *reinterpret_cast<float2 *>(po + 2 + d0) = make_float2(t.o[dt][0], t.o[dt][1]);
+                *reinterpret_cast<float2 *>(po + 4 + d0) = make_float2(t.o[dt][2], t.o[dt][3]);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // The rows of a sample share its K / V (flan-t5 beam search): attn_cross_shared_kernel over 128-key ranges, then the merge.  q: `rows` query
@@ -593,6 +665,51 @@ int launch_attn_decode_merge(const float *part, bf16 *out, int batch, int heads,
     return EILEV_OK;
 }
 
+// ---- DecodeAttnArgs.shared_prompt: the beam form with the prompt part shared among a sample's rows ------------------------------------------
+// Records per (row, head): [0, np) the prompt ranges of kSharedPromptKeys keys (attn_shared_prompt_kernel, one workgroup per (head, sample,
+// range)), [np, np + ng) the 128-key ranges of the generated keys [seq_len, seq_len + cap_g) (attn_decode_part_kernel<.., BEAM, 128, WIN>, per
+// row through the ancestor table: it stores and scores this step's K / V as the plain beam form does); one merge, or none where the caller
+// merges (a.out == nullptr).
+constexpr int kSharedGenKeys = 128;
+int attn_decode_shared_nsplit(int seq_len, int cap_g) { return (int)(ceil_div64(seq_len, kSharedPromptKeys) + ceil_div64(cap_g, kSharedGenKeys)); }
+size_t attn_decode_shared_part_bytes(int batch, int heads, int hd, int seq_len, int cap_g) {
+    return sizeof(float) * (size_t)batch * heads * attn_decode_shared_nsplit(seq_len, cap_g) * (hd + 2);
+}
+static int launch_attn_decode_shared(const DecodeAttnArgs &a, hipStream_t s, int *nsplit) {
+    if (!a.anc || !a.state || !a.fuse_new || a.rel_tab || a.out_frag) return EILEV_E_UNSUPPORTED;  // the beam form of a decode step only
+    if (!a.qkv || !a.kc || !a.vc || !a.kg || !a.vg || !a.part) return EILEV_E_BADARG;
+    if (a.batch <= 0 || a.batch > 32 || a.beams <= 0 || a.batch % a.beams || a.heads <= 0 || a.seq_len <= 0 || a.cap < a.seq_len || a.cap_g <= 0 ||
+        a.q_stride() < 3 * (int64_t)a.heads * a.hd || (a.q_stride() & 7))
+        return EILEV_E_BADARG;
+    if ((((uintptr_t)a.qkv | (uintptr_t)a.kc | (uintptr_t)a.vc | (uintptr_t)a.kg | (uintptr_t)a.vg | (uintptr_t)a.part) & 15) != 0) return EILEV_E_BADARG;
+    if (a.hd != 80 && a.hd != 128) return EILEV_E_UNSUPPORTED;
+    if (a.part_bytes < attn_decode_shared_part_bytes(a.batch, a.heads, a.hd, a.seq_len, a.cap_g)) return EILEV_E_WORKSPACE;
+    constexpr int TILES = kSharedPromptKeys / 64;
+    const int np = (int)ceil_div64(a.seq_len, kSharedPromptKeys), ng = (int)ceil_div64(a.cap_g, kSharedGenKeys), ns = np + ng;
+    const int64_t ldq = a.q_stride();
+    bf16 *kc = const_cast<bf16 *>(a.kc), *vc = const_cast<bf16 *>(a.vc);
+    const dim3 gp(a.heads, a.batch / a.beams, np), gg(a.heads, a.batch, ng);
+    if (a.hd == 80) {
+        hipLaunchKernelGGL((attn_shared_prompt_kernel<96, TILES>), gp, dim3(256), 0, s, a.qkv, ldq, a.kc, a.vc, a.part, a.attn_mask, a.beams, a.seq_len, a.cap,
+                           a.heads, a.hd, ns);
+        EILEV_LAUNCH_CHECK();
+        hipLaunchKernelGGL((attn_decode_part_kernel<10, 6, true, kSharedGenKeys, true>), gg, dim3(256), 0, s, a.qkv, kc, vc, a.part, a.attn_mask, a.state,
+                           a.seq_len, a.cap, a.heads, ldq, a.kg, a.vg, a.anc, a.beams, a.cap_g, a.batch, np, ns);
+    } else {
+        hipLaunchKernelGGL((attn_shared_prompt_kernel<128, TILES>), gp, dim3(256), 0, s, a.qkv, ldq, a.kc, a.vc, a.part, a.attn_mask, a.beams, a.seq_len, a.cap,
+                           a.heads, a.hd, ns);
+        EILEV_LAUNCH_CHECK();
+        hipLaunchKernelGGL((attn_decode_part_kernel<16, 8, true, kSharedGenKeys, true>), gg, dim3(256), 0, s, a.qkv, kc, vc, a.part, a.attn_mask, a.state,
+                           a.seq_len, a.cap, a.heads, ldq, a.kg, a.vg, a.anc, a.beams, a.cap_g, a.batch, np, ns);
+    }
+    EILEV_LAUNCH_CHECK();
+    if (!a.out) {  // the caller merges the partials itself (gemv.hip: in the prologue of out_proj)
+        *nsplit = ns;
+        return EILEV_OK;
+    }
+    return launch_attn_decode_merge(a.part, a.out, a.batch, a.heads, a.hd, ns, s);
+}
+
 static int g_beam_part = 1;
 static int g_attn_part32 = 1;  // 1 = by batch size (launch_attn_decode); probe build: 0 = the 256-key split kernel, 2 / 3 = force a form
 #ifdef EILEV_PROBES
@@ -609,6 +726,7 @@ bool attn_decode_loop_ok(const DecodeAttnArgs &a) {
 }
 int launch_attn_decode(const DecodeAttnArgs &a, hipStream_t s, int *nsplit) {
     if (!a.out && !nsplit) return EILEV_E_BADARG;  // partials are left only to a caller that merges them
+    if (a.shared_prompt) return launch_attn_decode_shared(a, s, nsplit);  // (asked for: what it does not take is an error, never another kernel)
     if (a.out_frag && !attn_decode_loop_ok(a)) return EILEV_E_UNSUPPORTED;
     const int batch = a.batch, heads = a.heads, hd = a.hd, cap_all = a.keys();  // beam form: prompt keys (prefill cache) + generated keys (generation cache)
     if (hd > 128 || (hd & 7)) return EILEV_E_UNSUPPORTED;

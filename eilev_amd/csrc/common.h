@@ -520,11 +520,18 @@ struct DecodeAttnArgs {
     const int32_t *anc = nullptr;
     int beams = 1, cap_g = 0;
     int out_frag = 0;                 // `out` in the row-block layout (frag32_index): attn_decode_loop_kernel only (attn_decode_loop_ok)
+    // beam form, head sizes 80 / 128: the prompt keys of a sample are read ONCE for its `beams` rows (attn_shared_prompt_kernel), the generated
+    // keys per row in 128-key ranges that start at seq_len; partials of attn_decode_shared_part_bytes in `part`, attn_mask may be null
+    int shared_prompt = 0;
     int64_t q_stride() const { return ldq ? ldq : 3 * (int64_t)heads * hd; }
     int keys() const { return anc ? seq_len + cap_g : cap; }  // the cache slots a row can attend to
 };
 // partials of `keys` keys in ranges of `range` keys; the 128-key ranges (the default) need the most of any form
 size_t attn_decode_part_bytes(int batch, int heads, int hd, int keys, int range = 128);
+// shared_prompt: key ranges per (row, head) = prompt ranges of kSharedPromptKeys keys + 128-key ranges of the cap_g generated keys, and their bytes
+constexpr int kSharedPromptKeys = 128;
+int attn_decode_shared_nsplit(int seq_len, int cap_g);
+size_t attn_decode_shared_part_bytes(int batch, int heads, int hd, int seq_len, int cap_g);
 bool attn_decode_loop_ok(const DecodeAttnArgs &a);  // the launch takes attn_decode_loop_kernel: the only form that writes the row-block layout
 // The merged rows into a.out, the kernel chosen by batch size, head size and flags.  a.out == nullptr: the partials of the 256-key split
 // kernel stay in a.part for the caller to merge (gemv_rows_kernel's prologue), *nsplit = their ranges per (row, head).

@@ -468,22 +468,39 @@ __global__ void bump_step_kernel(int32_t *state) {
 // One decode step of beam search WITHOUT moving the KV cache (include/eilev.h): the prompt's keys / values stay in the prefill cache, one
 // row per SAMPLE; the generated tokens' in a generation cache, one row per beam SLOT; `ancestors[g][r]` names the slot that holds the g-th
 // generated token of the hypothesis now living in row r.  (Before: torch index_select of the whole cache per step — 1.6 GB at 5 beams.)
-extern "C" int eilev_opt_decode_step_beam(const EilevDims *d, const EilevOptWeights *w, const int64_t *tokens, int32_t *state,
-                                          const int32_t *attn_mask, const int32_t *n_valid, int64_t rows, int64_t beams, int64_t seq_len,
-                                          const void *kv_prompt, void *kv_gen, int64_t gen_capacity, const int32_t *ancestors, float *logits,
-                                          void *workspace, size_t workspace_bytes, void *stream) {
+// shared_prompt (include/eilev_prefix.h eilev_prefix_decode_step): the attention reads a sample's prompt keys once for its rows
+// (DecodeAttnArgs.shared_prompt); its partials lie behind the step's own workspace
+size_t opt_decode_step_beam_shared_bytes(const EilevDims *d, int64_t rows, int64_t seq_len, int64_t gen_capacity) {
+    if (!d || !dims_ok_opt(d) || rows <= 0 || rows > 32 || seq_len <= 0 || gen_capacity <= 0 || seq_len + gen_capacity > (1 << 20)) return 0;
+    return align_up(eilev_opt_workspace_bytes(d, rows, 1), 256) +
+           attn_decode_shared_part_bytes((int)rows, d->t_heads, d->t_hidden / d->t_heads, (int)seq_len, (int)gen_capacity);
+}
+int opt_decode_step_beam(const EilevDims *d, const EilevOptWeights *w, const int64_t *tokens, int32_t *state, const int32_t *attn_mask,
+                         const int32_t *n_valid, int64_t rows, int64_t beams, int64_t seq_len, const void *kv_prompt, void *kv_gen, int64_t gen_capacity,
+                         const int32_t *ancestors, float *logits, void *workspace, size_t workspace_bytes, void *stream, int shared_prompt) {
     if (!d || !w || !tokens || !state || !attn_mask || !n_valid || !kv_prompt || !kv_gen || !ancestors || !logits || !workspace) return EILEV_E_BADARG;
     if (rows <= 0 || beams <= 0 || rows % beams || seq_len <= 0 || gen_capacity <= 0 || rows > 32) return EILEV_E_BADARG;
     if (!dims_ok_opt(d)) return EILEV_E_UNSUPPORTED;
+    const int D = d->t_hidden, H = d->t_heads, hd = D / H;
+    if (shared_prompt) {
+        if (hd != 80 && hd != 128) return EILEV_E_UNSUPPORTED;
+        if (seq_len + gen_capacity > (1 << 20) || (((uintptr_t)kv_prompt | (uintptr_t)kv_gen | (uintptr_t)workspace) & 15) != 0) return EILEV_E_BADARG;
+        if (workspace_bytes < opt_decode_step_beam_shared_bytes(d, rows, seq_len, gen_capacity)) return EILEV_E_WORKSPACE;
+    }
     if (workspace_bytes < eilev_opt_workspace_bytes(d, rows, 1)) return EILEV_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int D = d->t_hidden, H = d->t_heads, hd = D / H;
     const int64_t samples = rows / beams;
     const OptBufs b = carve_opt(d, rows, workspace);
     // block 0's attention: the prompt's keys in kv_prompt [layers][k | v][samples][heads][seq_len][hd], the generated ones in kv_gen (a row per beam slot)
     const KvCache kp(samples, D, seq_len), kg(rows, D, gen_capacity);
     DecodeAttnArgs a = decode_attn_args(b.qkv, b.att, b.scratch, rows, H, hd);
-    if (attn_decode_part_bytes((int)rows, H, hd, (int)(seq_len + gen_capacity)) > a.part_bytes) return EILEV_E_WORKSPACE;
+    if (shared_prompt) {
+        a.shared_prompt = 1;
+        a.part = reinterpret_cast<float *>((char *)workspace + align_up(eilev_opt_workspace_bytes(d, rows, 1), 256));
+        a.part_bytes = attn_decode_shared_part_bytes((int)rows, H, hd, (int)seq_len, (int)gen_capacity);
+    } else if (attn_decode_part_bytes((int)rows, H, hd, (int)(seq_len + gen_capacity)) > a.part_bytes) {
+        return EILEV_E_WORKSPACE;
+    }
     a.kc = kp.k((const bf16 *)kv_prompt, 0); a.vc = kp.v((const bf16 *)kv_prompt, 0); a.attn_mask = attn_mask; a.state = state; a.seq_len = a.cap = (int)seq_len; a.fuse_new = 1;
     a.kg = kg.k((bf16 *)kv_gen, 0); a.vg = kg.v((bf16 *)kv_gen, 0); a.anc = ancestors; a.beams = (int)beams; a.cap_g = (int)gen_capacity;
     RC(launch_decode_embed((const bf16 *)w->embed_tokens, (const bf16 *)w->embed_positions, tokens, n_valid, state, d->vocab, d->max_pos + 1, b.h,
@@ -492,4 +509,11 @@ extern "C" int eilev_opt_decode_step_beam(const EilevDims *d, const EilevOptWeig
     bump_step_kernel<<<1, 64, 0, s>>>(state);  // the step counter lives on the device: a captured step replays for every step
     EILEV_LAUNCH_CHECK();
     return EILEV_OK;
+}
+extern "C" int eilev_opt_decode_step_beam(const EilevDims *d, const EilevOptWeights *w, const int64_t *tokens, int32_t *state,
+                                          const int32_t *attn_mask, const int32_t *n_valid, int64_t rows, int64_t beams, int64_t seq_len,
+                                          const void *kv_prompt, void *kv_gen, int64_t gen_capacity, const int32_t *ancestors, float *logits,
+                                          void *workspace, size_t workspace_bytes, void *stream) {
+    return opt_decode_step_beam(d, w, tokens, state, attn_mask, n_valid, rows, beams, seq_len, kv_prompt, kv_gen, gen_capacity, ancestors, logits, workspace,
+                                workspace_bytes, stream, 0);
 }

@@ -12,6 +12,9 @@
 //      the q|k|v rows of this call: key s' is visible to query s iff it belongs to the same row and s' <= s (row ids of the tile's keys
 //      are worked out once per tile into LDS).
 // No per-row cache is ever read.  Every global read is guarded by an index check; the only writes go to `out`, rows < rows * new_len.
+//
+// The decode entries at the end (eilev_prefix_decode_*) own no kernel: the beam form of the OPT decode step (opt.hip opt_decode_step_beam)
+// with DecodeAttnArgs.shared_prompt set, whose attention is attn_decode.hip's launch_attn_decode_shared.
 #include "../../include/eilev_prefix.h"
 #include "attn_tile64.h"
 #include "stages.h"
@@ -175,4 +178,39 @@ extern "C" int eilev_prefix_extend(const EilevDims *d, const EilevOptWeights *w,
         RC(launch_gemm(g, 5, s));
     }
     return EILEV_OK;
+}
+
+static_assert(EILEV_PREFIX_DECODE_PROMPT_KEYS == kSharedPromptKeys, "the header states the record count of a launch");
+// ---- decoding with the prompt part of the attention shared among a sample's rows (common.h DecodeAttnArgs.shared_prompt) -----------------------
+extern "C" int eilev_prefix_decode_attention(const void *qkv, int64_t ldq, const void *k_prompt, const void *v_prompt, int64_t seq_len,
+                                             int64_t prompt_cap, const int32_t *attn_mask, const int32_t *state, void *k_gen, void *v_gen,
+                                             int64_t gen_capacity, const int32_t *ancestors, int64_t rows, int64_t beams, int64_t heads, int64_t head_dim,
+                                             void *out, void *part, size_t part_bytes, void *stream) {
+    if (!qkv || !k_prompt || !v_prompt || !state || !k_gen || !v_gen || !ancestors || !out || !part) return EILEV_E_BADARG;
+    if (rows <= 0 || beams <= 0 || rows % beams || rows > EILEV_PREFIX_DECODE_MAX_ROWS || heads <= 0 || heads > 1024 || head_dim <= 0 || head_dim > 1024 || (head_dim & 7)) return EILEV_E_BADARG;
+    if (seq_len <= 0 || prompt_cap < seq_len || prompt_cap > (1 << 20) || gen_capacity <= 0 || gen_capacity > (1 << 20)) return EILEV_E_BADARG;
+    if (ldq < 3 * heads * head_dim || ldq > (1 << 24) || (ldq & 7)) return EILEV_E_BADARG;
+    if (!aligned16(qkv) || !aligned16(k_prompt) || !aligned16(v_prompt) || !aligned16(k_gen) || !aligned16(v_gen) || !aligned16(out) || !aligned16(part))
+        return EILEV_E_BADARG;
+    if (head_dim != 80 && head_dim != 128) return EILEV_E_UNSUPPORTED;
+    DecodeAttnArgs a;
+    a.qkv = (const bf16 *)qkv; a.ldq = ldq; a.kc = (const bf16 *)k_prompt; a.vc = (const bf16 *)v_prompt; a.out = (bf16 *)out;
+    a.attn_mask = attn_mask; a.state = state; a.batch = (int)rows; a.seq_len = (int)seq_len; a.cap = (int)prompt_cap; a.heads = (int)heads; a.hd = (int)head_dim;
+    a.part = (float *)part; a.part_bytes = part_bytes; a.fuse_new = 1;
+    a.kg = (bf16 *)k_gen; a.vg = (bf16 *)v_gen; a.anc = ancestors; a.beams = (int)beams; a.cap_g = (int)gen_capacity;
+    a.shared_prompt = 1;
+    return launch_attn_decode(a, (hipStream_t)stream);
+}
+
+extern "C" size_t eilev_prefix_decode_workspace_bytes(const EilevDims *d, int64_t rows, int64_t seq_len, int64_t gen_capacity) {
+    if (!d || (d->t_heads > 0 && d->t_hidden / d->t_heads != 80 && d->t_hidden / d->t_heads != 128)) return 0;
+    return opt_decode_step_beam_shared_bytes(d, rows, seq_len, gen_capacity);
+}
+
+extern "C" int eilev_prefix_decode_step(const EilevDims *d, const EilevOptWeights *w, const int64_t *tokens, int32_t *state, const int32_t *attn_mask,
+                                        const int32_t *n_valid, int64_t rows, int64_t beams, int64_t seq_len, const void *kv_prompt, void *kv_gen,
+                                        int64_t gen_capacity, const int32_t *ancestors, float *logits, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+    return opt_decode_step_beam(d, w, tokens, state, attn_mask, n_valid, rows, beams, seq_len, kv_prompt, kv_gen, gen_capacity, ancestors, logits, workspace,
+                                workspace_bytes, stream, 1);
 }

@@ -128,5 +128,13 @@ int opt_qkv(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &
 int opt_tail(const EilevDims *d, const EilevOptWeights *w, int l, const OptBufs &b, int64_t M, hipStream_t s, const void *next_ln_w = nullptr,
              const void *next_ln_b = nullptr, int frag = 0, bool dry = false);
 
+// opt.hip: the body of eilev_opt_decode_step_beam (include/eilev.h: same arguments, same contract).  shared_prompt: the attention reads a
+// sample's prompt keys once for its rows (common.h DecodeAttnArgs.shared_prompt; head sizes 80 / 128, else EILEV_E_UNSUPPORTED) and the
+// workspace holds opt_decode_step_beam_shared_bytes (0 for arguments the step refuses): include/eilev_prefix.h eilev_prefix_decode_step
+int opt_decode_step_beam(const EilevDims *d, const EilevOptWeights *w, const int64_t *tokens, int32_t *state, const int32_t *attn_mask,
+                         const int32_t *n_valid, int64_t rows, int64_t beams, int64_t seq_len, const void *kv_prompt, void *kv_gen, int64_t gen_capacity,
+                         const int32_t *ancestors, float *logits, void *workspace, size_t workspace_bytes, void *stream, int shared_prompt);
+size_t opt_decode_step_beam_shared_bytes(const EilevDims *d, int64_t rows, int64_t seq_len, int64_t gen_capacity);
+
 // probe / test switches read outside the unit that defines them (set by eilev_debug_* of the probe build)
 extern int g_decode_rows;  // opt.hip; eilev_linear_rows (blocks.hip) follows it

@@ -49,7 +49,11 @@ class HipEngine:
         self._decode_warm = False
         self._dec_cache = None  # most recent captured decode step + the buffers it is bound to
         self._ctx_cache = None  # ... and that of greedy_decode_context (rows after a shared prefix)
-        self.context_stats = None    # per greedy_decode_context call: dict(path="shared", rows=, prefix=, new=, steps=)
+        self.context_stats = None    # per greedy_decode_context call: dict(path="shared", rows=, prefix=, new=, steps=) (+ reads="shared" with the switch below)
+        # opt-in: OPT beam search and the rows after a context run eilev_prefix_decode_step (include/eilev_prefix.h), whose attention reads a
+        # sample's prompt keys once for all its rows, in place of eilev_opt_decode_step_beam, which reads them once per row
+        self.shared_prompt_reads = False
+        self.beam_stats = None       # per beam_decode call that reached the beam-form step: dict(rows=, beams=, prompt=, reads="shared" | "per_row")
         self.device_sampling = True  # generate(do_sample=True, num_beams=1): the draw runs in the captured step (sample_decode_device); False: the host loop
         self.sample_stats = None     # per sampling call: dict(path="device" | "host", steps=generated tokens per row)
         self.device_rules = True     # greedy / beam search with repetition_penalty, no_repeat_ngram_size, min_new_tokens or several EOS ids: the
@@ -676,7 +680,7 @@ class HipEngine:
                 return ids
 
             out = self._chunked_rows(part, R, pad_id)
-            self.context_stats = dict(path="shared", rows=R, prefix=ctx.P, new=n, steps=max(stats))
+            self.context_stats = dict(path="shared", rows=R, prefix=ctx.P, new=n, steps=max(stats), **self._reads_record(getattr(self, "shared_prompt_reads", False)))
             return out
         eos = eos_list(eos_id)
         if len(eos) > 1:
@@ -685,7 +689,9 @@ class HipEngine:
         if n_dec > 0:
             self.ensure_stream_layout(R)
         graphable = use_graph and n_dec > 1 and trace is None
-        key = (ctx.kv.data_ptr(), P, R, n, max_new_tokens, tuple(eos), int(pad_id))
+        shared = bool(getattr(self, "shared_prompt_reads", False))
+        step_fn, step_name, ws_bytes = self._beam_form_step(shared, R, P, gen_cap)
+        key = (ctx.kv.data_ptr(), P, R, n, max_new_tokens, tuple(eos), int(pad_id), shared)
         ent = self._ctx_cache if (graphable and self._ctx_cache is not None and self._ctx_cache["key"] == key) else None
         if ent is None:
             ent = dict(key=key, graph=None, ctx=ctx,  # (the entry keeps the context alive: its graph holds the prefix cache's address)
@@ -699,7 +705,7 @@ class HipEngine:
                        tokens=torch.zeros(R, dtype=torch.int64, device=self.device),
                        out=torch.empty((R, max_new_tokens), dtype=torch.int64, device=self.device),
                        logits=torch.empty((R, d.vocab), dtype=torch.float32, device=self.device),
-                       ws=self._workspace("dec", self.lib.eilev_opt_workspace_bytes(C.byref(d), R, 1)))
+                       ws=self._workspace("dec", ws_bytes))
             if graphable:
                 self._ctx_cache = None
                 self._ctx_cache = ent
@@ -716,17 +722,36 @@ class HipEngine:
         self._greedy_select(last, R, d.vocab, sel_state, finished, eos1, pad_id, tokens, out)
 
         def one_step():
-            abi.check(self.lib.eilev_opt_decode_step_beam(
+            abi.check(step_fn(
                 C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(step_state), _ptr(am), _ptr(n_valid), R, R, P, _ptr(ctx.kv), _ptr(kv_rows),
-                gen_cap, _ptr(anc), _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_opt_decode_step_beam")
+                gen_cap, _ptr(anc), _ptr(logits), _ptr(ws), ws.numel(), self._stream()), step_name)
             self._greedy_select(logits, R, d.vocab, sel_state, finished, eos1, pad_id, tokens, out)
 
         graph = ent["graph"] if graphable else None
         if graphable and graph is None:  # (the warm run writes KV slot n of every row, as the first replay does)
             graph = ent["graph"] = self._capture_step(one_step, (step_state, sel_state, finished, tokens, out), warm=True)
         done = self._run_steps(n_dec, one_step, graph, sel_state, eos, poll_every, trace, logits)
-        self.context_stats = dict(path="shared", rows=R, prefix=P, new=n, steps=1 + done)
+        self.context_stats = dict(path="shared", rows=R, prefix=P, new=n, steps=1 + done, **self._reads_record(shared))
         return self._trim_at_eos(out, 1 + done, eos)
+
+    def _beam_form_step(self, shared, rows, seq_len, gen_cap):
+        """(entry, its name, workspace bytes) of the beam form of the OPT decode step: eilev_opt_decode_step_beam, or with ``shared`` its drop-in
+        eilev_prefix_decode_step (include/eilev_prefix.h) — no fallback: a model that step does not take is an error."""
+        d = self.dims
+        if not shared:
+            return self.lib.eilev_opt_decode_step_beam, "eilev_opt_decode_step_beam", self.lib.eilev_opt_workspace_bytes(C.byref(d), rows, 1)
+        if not abi.prefix_supported(d):
+            raise NotImplementedError("shared_prompt_reads: the shared-prompt decode step takes OPT head sizes 80 and 128")
+        px = abi.load_prefix()
+        nbytes = px.eilev_prefix_decode_workspace_bytes(C.byref(d), rows, seq_len, gen_cap)
+        if nbytes == 0:
+            raise ValueError(f"eilev_prefix_decode_step refuses rows={rows}, seq_len={seq_len}, gen_capacity={gen_cap}")
+        return px.eilev_prefix_decode_step, "eilev_prefix_decode_step", nbytes
+
+    @staticmethod
+    def _reads_record(shared):
+        """The ``reads`` entry of context_stats: present (reads="shared") only with the switch on, so the record of a plain call is what it was."""
+        return dict(reads="shared") if shared else {}
 
     def classify_loglik(self, prompt_embeds, prompt_mask, class_input_ids, class_attention_mask=None, class_batch_size=None,
                         share_prompt_cache=False):
@@ -931,15 +956,18 @@ class HipEngine:
         state = torch.zeros(2, dtype=torch.int32, device=self.device)
         tokens = torch.zeros(R, dtype=torch.int64, device=self.device)
         logits = torch.empty((R, d.vocab), dtype=torch.float32, device=self.device)
-        nb = self.lib.eilev_opt_workspace_bytes(C.byref(d), R, 1)
+        shared = bool(getattr(self, "shared_prompt_reads", False))
+        step_fn, step_name, nb = self._beam_form_step(shared, R, L, gen_cap)
+        warm_flag = "_shared_warm" if shared else "_decode_warm"  # (each library loads its kernels lazily: one warm run each)
         ws = self._workspace("dec", nb)
         steps = [0]
         graph = [None]
+        self.beam_stats = dict(rows=R, beams=num_beams, prompt=L, reads="shared" if shared else "per_row")
 
         def launch():
-            abi.check(self.lib.eilev_opt_decode_step_beam(
+            abi.check(step_fn(
                 C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), R, num_beams, L, _ptr(kv_prompt), _ptr(kv_gen),
-                gen_cap, _ptr(anc), _ptr(logits), _ptr(ws), ws.numel(), self._stream()), "eilev_opt_decode_step_beam")
+                gen_cap, _ptr(anc), _ptr(logits), _ptr(ws), ws.numel(), self._stream()), step_name)
 
         def step(next_tokens, beam_src):
             t = steps[0]  # tokens generated before this one
@@ -952,8 +980,8 @@ class HipEngine:
                 state[0] = 1  # (the call increments it: every per-step quantity is on the device, so ONE captured step replays)
             if use_graph and max_new_tokens > 2:
                 if graph[0] is None:  # (once per engine the launch also runs outside capture; it rewrote this step's slot only)
-                    graph[0] = self._capture_step(launch, (state,), warm=not self._decode_warm)
-                    self._decode_warm = True
+                    graph[0] = self._capture_step(launch, (state,), warm=not getattr(self, warm_flag, False))
+                    setattr(self, warm_flag, True)
                 graph[0].replay()
             else:
                 launch()
@@ -966,7 +994,7 @@ class HipEngine:
             # generated token, nothing indexed by the step on the host (eilev_amd/beam.py::beam_search_device)
             out = self._beam_device_loop(launch, last, B, num_beams, max_new_tokens, d.vocab, state, tokens, anc, logits, length_penalty, eos_id, pad_id,
                                          early_stopping, num_return_sequences, use_graph, plan.dev_kw, plan.topk_ok, plan.advance_ok)
-            self._decode_warm = True
+            setattr(self, warm_flag, True)
             return out
         return self._host_loop(plan, step, last, B, num_beams, max_new_tokens, length_penalty, eos_id, pad_id, early_stopping, num_return_sequences,
                                min_new_tokens)

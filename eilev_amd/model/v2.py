@@ -16,6 +16,8 @@ alone, for OPT and flan-t5, and the ``kv_cache_dtype="fp8"`` refusal is derived 
 64, without copying or replicating a cache: include/eilev_t5beam.h); beam-search sampling and user ``logits_processor`` / ``stopping_criteria`` / ``max_time`` keep the host loops.
 ``encode_context`` prefills a leading part that many calls share — the in-context examples — once; ``generate(context=...)`` and
 ``classify(share_prompt_cache=True)`` then run their rows over that one cached prefix (include/eilev_prefix.h; plain greedy search on OPT).
+``generate(shared_prompt_reads=True)`` (opt-in; ``context=`` or ``num_beams > 1`` on OPT) runs the decode step whose attention reads a sample's
+prompt keys once for all its rows (include/eilev_prefix.h eilev_prefix_decode_step).
 ``generate(kv_cache_dtype="fp8")`` keeps the OPT decode step's KV cache in e4m3 bytes with power-of-two scales (include/eilev_kv8.h; greedy
 search, sampling and the logits rules on their device routes).
 ``output_hidden_states`` / ``output_attentions`` inside the full model's ``forward`` are served from slow paths for the vision wrapper,
@@ -620,6 +622,20 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
                 raise NotImplementedError("generate(output_scores / output_logits) is served for greedy search on the decoder-only language model only")
             if len(eos_ids) > 8:
                 raise NotImplementedError("prompt_lookup_num_tokens takes at most 8 EOS ids")
+        # shared prompt reads (opt-in): the decode step of beam search and of the rows after a context reads a sample's prompt keys once for
+        # all its rows (include/eilev_prefix.h eilev_prefix_decode_step); refused here, by name, where no such step runs
+        shared_reads = bool(kw.pop("shared_prompt_reads", False))
+        if shared_reads:
+            t_cfg = self.config.text_config
+            heads = int(getattr(t_cfg, "num_attention_heads", 0) or 0)
+            head_size = None if self._is_t5 or not heads else int(t_cfg.hidden_size) // heads
+            combo = [n for n, on in (("the flan-t5 language model (its beam search shares the encoder's keys already)", self._is_t5),
+                                     (f"head size {head_size} (the shared-prompt decode step takes 80 and 128)", not self._is_t5 and head_size not in (80, 128)),
+                                     ("prompt_lookup_num_tokens", lookup is not None),
+                                     ("one row per prompt and no context= (no rows share a prompt)", num_beams == 1 and context is None)) if on]
+            if combo:
+                raise NotImplementedError(f"generate(shared_prompt_reads=True) with {', '.join(combo)} is not built on the HIP path (OPT beam search and "
+                                          "generate(context=...) at head sizes 80 / 128 are)")
         if kw:
             raise NotImplementedError(f"unsupported generate() arguments on the HIP path: {sorted(kw)}")
         if context is not None:  # v1: plain greedy search over a shared prefix; everything is checked here, before any encode
@@ -649,7 +665,7 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         return SimpleNamespace(context=context, kv_dtype=kv_dtype, num_beams=num_beams, do_sample=do_sample, length_penalty=float(length_penalty),
                                early_stopping=early_stopping, num_return=int(num_return), sampler=sampler, max_new=int(max_new), min_new=min_new,
                                eos_ids=eos_ids, eos1=eos1, eos_arg=eos_ids if with_rules else eos1, pad=int(pad), rules=rules, lookup=lookup,
-                               lookup_ngram=lookup_ngram, want_dict=want_dict, want_scores=want_scores, want_logits=want_logits)
+                               lookup_ngram=lookup_ngram, want_dict=want_dict, want_scores=want_scores, want_logits=want_logits, shared_reads=shared_reads)
 
     @torch.no_grad()
     def generate(self, input_ids, pixel_values=None, video_input_mask=None, attention_mask=None, **generate_kwargs):
@@ -677,6 +693,15 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
             if combo or plan.route not in route.CAPTURED:
                 raise NotImplementedError(f"generate(kv_cache_dtype='fp8') with {', '.join(combo)} is not built on the HIP path (greedy search, sampling "
                                           "and the logits rules of the captured OPT decode step are)")
+        if r.shared_reads:  # the engine's switch for the duration of this call; everything else is the call without the keyword
+            plain = {k: v for k, v in generate_kwargs.items() if k != "shared_prompt_reads"}
+            eng = self.engine()
+            was = getattr(eng, "shared_prompt_reads", False)
+            eng.shared_prompt_reads = True
+            try:
+                return self.generate(input_ids, pixel_values=pixel_values, video_input_mask=video_input_mask, attention_mask=attention_mask, **plain)
+            finally:
+                eng.shared_prompt_reads = was
         if r.want_dict and not (r.want_scores or r.want_logits):  # sequences only: any decoding mode, wrapped like hf wraps it
             from transformers.generation.utils import GenerateDecoderOnlyOutput, GenerateEncoderDecoderOutput
 
@@ -768,7 +793,8 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         out = torch.full((B, width), pad, dtype=torch.int64, device=emb.device)
         for n, rows in groups.items():
             out[torch.tensor(rows, device=emb.device), : parts[n].shape[1]] = parts[n]
-        eng.context_stats = dict(path="shared", rows=B, prefix=context.P, new=max(groups), steps=steps)
+        eng.context_stats = dict(path="shared", rows=B, prefix=context.P, new=max(groups), steps=steps,
+                                 **{k: v for k, v in (eng.context_stats or {}).items() if k == "reads"})
         return out
 
     @torch.no_grad()
