@@ -183,20 +183,29 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
 
     load_tile<DP>(qp, a.ldq, q0, a.sq, a.hd, Qs, nullptr, tid);
     load_tile<DP>(dop, a.ldo, q0, a.sq, a.hd, dOs, nullptr, tid);
-    if (tid < 64) delta_s[tid] = 0.0f;
     __syncthreads();
-    {  // delta[q] = sum_d o * d_o (d_o from the tile just staged)
+    {  // delta[q] = sum_d o * d_o (d_o from the tile just staged): one partial per 8-column chunk, then summed per row in chunk order.
+       // (LDS atomics gave an order that depends on wave timing where a row's CH chunks straddle two waves: CH = 12, hd 72..96.)
         constexpr int CH = DP / 8;
+        float *dpart = reinterpret_cast<float *>(dSs);  // [64][CH] <= 4 KB of the dS tile, which pass 2 writes first
         for (int i = tid; i < 64 * CH; i += 256) {
             const int r = i / CH, c = i - r * CH;
+            float s = 0.0f;
             if (q0 + r < a.sq && c * 8 < a.hd) {
-                float ov[8], gv[8], s = 0.0f;
+                float ov[8], gv[8];
                 unpack8(*reinterpret_cast<const bf16x8 *>(op + (int64_t)(q0 + r) * a.ldo + c * 8), ov);
                 unpack8(*reinterpret_cast<const bf16x8 *>(dOs + r * LDR + c * 8), gv);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s += ov[e] * gv[e];
-                atomicAdd(&delta_s[r], s);
             }
+            dpart[i] = s;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            float s = 0.0f;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) s += dpart[tid * CH + c];
+            delta_s[tid] = s;
         }
     }
 
