@@ -295,7 +295,7 @@ bool w6_ok(const GemmArgs &g) {
 // The old rule (w6 below 1024 tiles) stays for N that is not a whole number of 256-column tiles.
 bool w6_pick(const GemmArgs &g) {
     const int64_t tm256 = ceil_div64(g.M, 256), tiles256 = tm256 * ceil_div64(g.N, 256);
-    const int n_cu_q = eilev_num_cu() / 8 * 8;  // (the device's CUs in both builds: the probe build's grid override moves the M <= 32 family only)
+    const int n_cu_q = eilev_num_cu() / 8 * 8;  // (the device's CUs in both builds: the probe build's grid override moves the M <= 32 family and the M <= 8 row-dot kernels of gemv.hip, not this rule)
     auto fill = [&](int64_t t) { return (double)t / (double)(ceil_div64(t, n_cu_q) * n_cu_q); };
     return g.N % 256 == 0 ? 1.06 * fill(tiles256) < fill(tm256 * ceil_div64(g.N, 128)) : tiles256 < 1024;
 }

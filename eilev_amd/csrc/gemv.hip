@@ -17,6 +17,10 @@
 // values the separate LayerNorm / merge kernels would have stored); v_dot2c_f32_bf16 accumulates in fp32; 6 xor-shuffle steps reduce
 // the 64 lane partials; the epilogue (bias, q scaling, ReLU, residual) runs on lane 0..M-1.
 // HBM-bound: the weight bytes are read exactly once; the activations (M x K x 2 B) come from L2 once per workgroup.
+//
+// Tests: tests/test_hip_gemv.py launches every kernel template of this file on its own through eilev_debug_gemv (probe build, end of this
+// file) and holds each output element to the float64 reference and bound of tests/gemv_ref.py (tests/test_gemv_reference.py checks those on
+// the CPU); tests/test_gemv_rows.py runs the public eilev_linear_rows at the workload shapes against the CPU oracle.
 #include "common.h"
 #include <type_traits>
 #include <utility>
@@ -27,6 +31,15 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 enum { PRO_X = 0, PRO_LN = 1, PRO_MERGE = 2 };
+
+// Probe build only: the kernel instance of the last launch, for eilev_debug_gemv (end of this file).  template (1 gemv_rows_kernel, 2 gemv1_kernel,
+// 3 gemvm_kernel) * 100000 + MR * 10000 + (CPS or NCH) * 100 + PRO * 10 + LONG.  The product library has neither the variable nor the writes.
+#ifdef EILEV_PROBES
+int g_gemv_instance = 0;
+#define GEMV_INSTANCE(tmpl, mr, geo, pro, lng) (g_gemv_instance = (tmpl) * 100000 + (mr) * 10000 + (geo) * 100 + (pro) * 10 + (lng))
+#else
+#define GEMV_INSTANCE(tmpl, mr, geo, pro, lng) ((void)0)
+#endif
 
 struct GemvArgs {
     const bf16 *x;  // PRO_X / PRO_LN: (M, K) rows, leading dimension ldx
@@ -205,6 +218,7 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const GemvArgs a) {
 
 template <int MR, int PRO, int CPS>
 int launch_rows_c(const GemvArgs &a, int grid, size_t smem, hipStream_t s) {
+    GEMV_INSTANCE(1, MR, CPS, PRO, 0);
     return eilev_launch<gemv_rows_kernel<MR, PRO, CPS>>(dim3(grid), dim3(256), smem, s, a);
 }
 
@@ -345,12 +359,15 @@ __global__ __launch_bounds__(320) void gemv1_kernel(const GemvArgs a) {
                 float l = 0.0f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int sp = 0; sp < 8; ++sp) {
-                    const float wgt = (sp < ns && ml[sp].y > 0.0f) ? __expf(ml[sp].x - mx) : 0.0f;
+                    const bool live = sp < ns && ml[sp].y > 0.0f;
+                    const float wgt = live ? __expf(ml[sp].x - mx) : 0.0f;
                     l += wgt * ml[sp].y;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        o[2 * q] += wgt * ov[sp][q].x;
-                        o[2 * q + 1] += wgt * ov[sp][q].y;
+                        // an empty range's o is unwritten memory (attn_decode_part_kernel stores only its max and sum): 0 * Inf or 0 * NaN must
+                        // not reach the row.  A select around the multiply-add, not a branch: the 40 loads above stay in flight together.
+                        o[2 * q] = live ? fmaf(wgt, ov[sp][q].x, o[2 * q]) : o[2 * q];
+                        o[2 * q + 1] = live ? fmaf(wgt, ov[sp][q].y, o[2 * q + 1]) : o[2 * q + 1];
                     }
                 }
                 bf16x8 v;
@@ -441,6 +458,7 @@ int launch_gemv1_c(const GemvArgs &a, int grid, hipStream_t s) {
     // registers: ring RB * SB * 4 + x NCH * 4 (K = 2560: 160 + 20; K = 10240: 80 + 80); the LayerNorm prologue holds the row as 8 NCH floats
     // beside the ring (RB = 8 spilled 204 VGPRs there)
     constexpr int RB = IPR == 1 ? (SB == 5 ? (PRO == PRO_LN ? 4 : 8) : (PRO == PRO_LN ? 2 : 4)) : 4;
+    GEMV_INSTANCE(2, 1, NCH, PRO, 0);
     hipLaunchKernelGGL((gemv1_kernel<NCH, PRO, SB, RB>), dim3(grid), dim3(320), 0, s, a);
     EILEV_LAUNCH_CHECK();
     return EILEV_OK;
@@ -604,6 +622,7 @@ int launch_gemvm_c(const GemvArgs &a, int grid, hipStream_t s) {
     constexpr int RB = (PRO == PRO_LN || MR >= 3) ? 4 : 8;
     const size_t smem = (size_t)MR * NCH * 512 * sizeof(bf16);
     // one code path per instance (both in one kernel doubled the register pressure): long waves only when EVERY wave has 2 RB items
+    GEMV_INSTANCE(3, MR, NCH, PRO, a.rows_per_wave * IPR >= 2 * RB ? 1 : 0);
     if (a.rows_per_wave * IPR >= 2 * RB) return eilev_launch<gemvm_kernel<MR, NCH, PRO, SB, RB, true>>(dim3(grid), dim3(320), smem, s, a);
     return eilev_launch<gemvm_kernel<MR, NCH, PRO, SB, RB, false>>(dim3(grid), dim3(320), smem, s, a);
 }
@@ -670,8 +689,9 @@ int launch_gemv1(int pro, const bf16 *x, const bf16 *gamma, const bf16 *beta, fl
         if (nsplit < 1 || nsplit > 8) return EILEV_E_UNSUPPORTED;
         if (!part || heads * hd != K || (hd & 7) || (K >> 9) != 5 || K % 512 || !W || !out || ((uintptr_t)W & 15) || ((uintptr_t)part & 7)) return EILEV_E_UNSUPPORTED;
     } else if (!gemv1_ok(N, K, pro) || !x || !W || !out || ((uintptr_t)x & 15) || ((uintptr_t)W & 15)) return EILEV_E_UNSUPPORTED;
+    if (N < 1 || ((bias || resid) && (N & 1))) return EILEV_E_UNSUPPORTED;  // bias / residual are fetched as 32-bit pairs (bias32[n >> 1]): even N only
     if ((bias && ((uintptr_t)bias & 3)) || (resid && ((uintptr_t)resid & 3)) || (pro == PRO_LN && (!gamma || !beta))) return EILEV_E_BADARG;
-    const int n_cu = eilev_num_cu();
+    const int n_cu = eilev_grid_cus();  // (the device's CUs; the probe build's eilev_debug_grid_cus shrinks the grid so that small N reach the long-wave paths)
     GemvArgs a = {};
     a.x = x; a.ldx = K; a.gamma = gamma; a.beta = beta; a.eps = eps; a.W = W; a.bias = bias; a.resid = resid; a.ldr = N; a.out = out; a.ldo = N;
     a.out_f32 = out_f32; a.M = 1; a.N = N; a.K = K; a.epi = epi; a.scale = scale; a.scale_cols = scale_cols;
@@ -700,8 +720,9 @@ bool gemvm_ok(int M, int N, int K, int pro) {
 int launch_gemvm(int pro, const bf16 *x, int64_t ldx, const bf16 *gamma, const bf16 *beta, float eps, const bf16 *W, const bf16 *bias, const bf16 *resid,
                  int64_t ldr, void *out, int64_t ldo, int out_f32, int M, int N, int K, int epi, float scale, int scale_cols, hipStream_t s) {
     if (!gemvm_ok(M, N, K, pro) || !x || !W || !out || ((uintptr_t)x & 15) || (ldx & 7) || ((uintptr_t)W & 15)) return EILEV_E_UNSUPPORTED;
+    if ((bias || resid) && (N & 1)) return EILEV_E_UNSUPPORTED;  // 32-bit pair fetches of bias / residual, as in launch_gemv1
     if ((bias && ((uintptr_t)bias & 3)) || (resid && (((uintptr_t)resid & 3) || (ldr & 1))) || (pro == PRO_LN && (!gamma || !beta))) return EILEV_E_BADARG;
-    const int n_cu = eilev_num_cu();
+    const int n_cu = eilev_grid_cus();
     GemvArgs a = {};
     a.x = x; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.W = W; a.bias = bias; a.resid = resid; a.ldr = ldr; a.out = out; a.ldo = ldo;
     a.out_f32 = out_f32; a.M = M; a.N = N; a.K = K; a.epi = epi; a.scale = scale; a.scale_cols = scale_cols;
@@ -712,3 +733,43 @@ int launch_gemvm(int pro, const bf16 *x, int64_t ldx, const bf16 *gamma, const b
     if (pro == PRO_LN) return launch_gemvm_m<5, PRO_LN>(a, grid, s);
     return launch_gemvm_m<5, PRO_X>(a, grid, s);
 }
+
+#ifdef EILEV_PROBES
+// probe / test entry (tests/test_hip_gemv.py): ONE call of a launcher of this file on the caller's buffers — launcher 0 launch_gemv_rows,
+// 1 launch_gemv1 (M must be 1; ldx / ldr / ldo are not passed on: the launcher has none), 2 launch_gemvm (part / heads / hd / nsplit are not
+// passed on).  The struct is the launchers' arguments as plain pointers and integers (the ctypes mirror lives with the tests); struct_bytes
+// must be its size, so a stale mirror is refused instead of run.  *instance receives the code of the kernel instance that was launched
+// (GEMV_INSTANCE above; 0: none).  eilev_debug_grid_cus applies to launchers 1 and 2, whose grid follows the CU count.
+struct EilevDebugGemvArgs {
+    int32_t pro, pad0;
+    const void *x; int64_t ldx;
+    const void *gamma, *beta;
+    float eps; int32_t pad1;
+    const float *part;
+    int32_t heads, hd, nsplit, pad2;
+    const void *W, *bias, *resid; int64_t ldr;
+    void *out; int64_t ldo;
+    int32_t out_f32, M, N, K, epi;
+    float scale;
+    int32_t scale_cols, pad3;
+};
+extern "C" int eilev_debug_gemv(const EilevDebugGemvArgs *args, size_t struct_bytes, int launcher, int *instance, void *stream) {
+    if (!args || struct_bytes != sizeof(EilevDebugGemvArgs) || launcher < 0 || launcher > 2) return EILEV_E_BADARG;
+    if (launcher == 1 && args->M != 1) return EILEV_E_BADARG;
+    const EilevDebugGemvArgs &g = *args;
+    hipStream_t s = (hipStream_t)stream;
+    g_gemv_instance = 0;
+    int rc;
+    if (launcher == 0)
+        rc = launch_gemv_rows(g.pro, (const bf16 *)g.x, g.ldx, (const bf16 *)g.gamma, (const bf16 *)g.beta, g.eps, g.part, g.heads, g.hd, g.nsplit, (const bf16 *)g.W,
+                              (const bf16 *)g.bias, (const bf16 *)g.resid, g.ldr, g.out, g.ldo, g.out_f32, g.M, g.N, g.K, g.epi, g.scale, g.scale_cols, s);
+    else if (launcher == 1)
+        rc = launch_gemv1(g.pro, (const bf16 *)g.x, (const bf16 *)g.gamma, (const bf16 *)g.beta, g.eps, (const bf16 *)g.W, (const bf16 *)g.bias, (const bf16 *)g.resid,
+                          g.out, g.out_f32, g.N, g.K, g.epi, g.scale, g.scale_cols, s, g.part, g.heads, g.hd, g.nsplit);
+    else
+        rc = launch_gemvm(g.pro, (const bf16 *)g.x, g.ldx, (const bf16 *)g.gamma, (const bf16 *)g.beta, g.eps, (const bf16 *)g.W, (const bf16 *)g.bias,
+                          (const bf16 *)g.resid, g.ldr, g.out, g.ldo, g.out_f32, g.M, g.N, g.K, g.epi, g.scale, g.scale_cols, s);
+    if (instance) *instance = g_gemv_instance;
+    return rc;
+}
+#endif
