@@ -756,6 +756,67 @@ def load_kv8() -> C.CDLL:
     return _load_companion(KV8_LIB_PATH, KV8_ABI_VERSION, declare)
 
 
+# ---- the int4 weight-only companion library (include/eilev_w4.h): the M <= 32 linear over 4-bit codes with group scales, the expansion of
+# the format into its bf16 twin, and the OPT decode step on them.  It carries its own copy of the core library's code and shares no state with it. ----
+W4_LIB_PATH = os.path.join(_HERE, "csrc", "libeilev_hip_w4.so")
+W4_ABI_VERSION = 1
+W4_GROUP = 128
+W4_KTILE = 256
+W4_MAX_ROWS = 32
+W4_WAVE_TILES = 3
+W4_EXPORTS = ["eilev_w4_abi_version", "eilev_w4_decode_step", "eilev_w4_expand", "eilev_w4_linear", "eilev_w4_linear_scratch_bytes", "eilev_w4_plan",
+              "eilev_w4_workspace_bytes"]
+
+
+class W4Matrix(C.Structure):
+    _fields_ = [("w4", vp), ("scales", vp)]
+
+
+class W4Layer(C.Structure):
+    _fields_ = [("qkv", W4Matrix), ("o", W4Matrix), ("fc1", W4Matrix), ("fc2", W4Matrix)]
+
+
+class W4Linear(C.Structure):
+    _fields_ = [("a", vp), ("lda", C.c_int64), ("w", W4Matrix), ("bias", vp), ("resid", vp), ("ldr", C.c_int64), ("c", vp), ("ldc", C.c_int64),
+                ("m", C.c_int64), ("n", C.c_int64), ("k", C.c_int64), ("relu", C.c_int32), ("out_f32", C.c_int32), ("scale", C.c_float),
+                ("scale_cols", C.c_int32), ("ln_gamma", vp), ("ln_beta", vp), ("ln_out", vp), ("ln_eps", C.c_float), ("scratch", vp),
+                ("scratch_bytes", C.c_size_t)]
+
+
+def w4_supported(dims) -> bool:
+    """The models eilev_w4_decode_step takes (anything else returns EILEV_E_UNSUPPORTED): OPT widths that are multiples of 256, hidden at
+    most 4096 (the LayerNorm rows ride on the split-K reduce of norm.hip)."""
+    return (dims is not None and 0 < int(dims.t_hidden) <= 4096 and int(dims.t_hidden) % W4_KTILE == 0 and int(dims.t_ffn) > 0 and
+            int(dims.t_ffn) % W4_KTILE == 0)
+
+
+def w4_plan(m: int, n: int, k: int):
+    """eilev_w4_plan restated: (MB, K splits, 16-row blocks, K splits, tiles per wave), or None for a shape it refuses."""
+    if m < 1 or m > W4_MAX_ROWS or n < 1 or k < 1 or k % W4_KTILE or k > 1 << 20 or n > 1 << 24:
+        return None
+    nb, ktiles = -(-n // 16), k // 256
+    ks = 1 if nb >= 384 else -(-512 // nb)
+    ks = min(ks, max(ktiles // 4, 1))
+    ks = max(ks, -(-ktiles // (4 * W4_WAVE_TILES)))
+    return (1 if m <= 16 else 2, ks, nb, ks, -(-(-(-ktiles // ks)) // 4))
+
+
+def load_w4() -> C.CDLL:
+    """Load libeilev_hip_w4.so."""
+    def declare(sig):
+        DP = C.POINTER(Dims)
+        sig("eilev_w4_expand", _i32, vp, vp, _i64, _i64, vp, vp)
+        sig("eilev_w4_plan", _i32, _i64, _i64, _i64, C.POINTER(C.c_int32))
+        sig("eilev_w4_linear_scratch_bytes", _sz, _i64, _i64, _i64)
+        sig("eilev_w4_linear", _i32, C.POINTER(W4Linear), vp)
+        sig("eilev_w4_workspace_bytes", _sz, DP, _i64)
+        sig("eilev_w4_decode_step", _i32, DP, C.POINTER(OptWeights), C.POINTER(W4Layer), vp, vp, vp, vp, _i64, _i64, vp, _i64, vp, vp, _i64, _i64, vp,
+            _i64, vp, _sz, vp)
+        return sig("eilev_w4_abi_version", _i32)
+
+    return _load_companion(W4_LIB_PATH, W4_ABI_VERSION, declare)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         names = {-1: "EILEV_E_BADARG", -2: "EILEV_E_UNSUPPORTED", -3: "EILEV_E_WORKSPACE"}

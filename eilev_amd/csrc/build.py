@@ -2,7 +2,7 @@
 sampling), libeilev_hip_rules.so (logits rules of greedy and beam search), libeilev_hip_t5beam.so (the flan-t5 decode step of beam search:
 its own unit t5beam.o linked with the core library's objects, include/eilev_t5beam.h) and libeilev_hip_prefix.so (rows that continue one
 shared prefix: prefix.o linked the same way, include/eilev_prefix.h) and libeilev_hip_kv8.so (the OPT decode step over an fp8 KV cache: kv8.o,
-include/eilev_kv8.h) (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
+include/eilev_kv8.h) and libeilev_hip_w4.so (the OPT decode step over int4 weight-only linears: w4.o, include/eilev_w4.h) (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
 from __future__ import annotations
 
 import os
@@ -33,7 +33,9 @@ T5BEAM = ("t5beam.hip", [os.path.join(_INC, "eilev_t5beam.h")], "exports_t5beam.
 PREFIX = ("prefix.hip", [os.path.join(_INC, "eilev_prefix.h")], "exports_prefix.map", "libeilev_hip_prefix.so")
 # libeilev_hip_kv8.so: the same arrangement for kv8.hip (the OPT decode step around its own fp8-cache attention kernel); only eilev_kv8_* is exported
 KV8 = ("kv8.hip", [os.path.join(_INC, "eilev_kv8.h")], "exports_kv8.map", "libeilev_hip_kv8.so")
-LINKED = (T5BEAM, PREFIX, KV8)  # (source, headers, export map, output): one unit each, linked with the core library's objects
+# libeilev_hip_w4.so: the same arrangement for w4.hip (the OPT decode step around its own int4 weight-streaming linear); only eilev_w4_* is exported
+W4 = ("w4.hip", [os.path.join(_INC, "eilev_w4.h")], "exports_w4.map", "libeilev_hip_w4.so")
+LINKED = (T5BEAM, PREFIX, KV8, W4)  # (source, headers, export map, output): one unit each, linked with the core library's objects
 
 
 def _hipcc() -> str:

@@ -7,6 +7,7 @@ constructing an engine without the built library or without a GPU raises.
 from __future__ import annotations
 
 import ctypes as C
+import gc
 
 import torch
 
@@ -31,6 +32,18 @@ class HipEngine:
 
     def __init__(self, config, named_tensors: dict, device=None, parts=None, lm_weights: str = "bf16", vit_ln_fold: bool = True,
                  decode_stream_layout: bool = True, vit_block_order: bool = True):
+        # the weight mode is checked from the arguments alone, before anything touches a device
+        if lm_weights not in ("bf16", "fp8", "fp8_mfma", "int4"):
+            raise ValueError("lm_weights must be 'bf16', 'fp8' (e4m3 weights, bf16 activations), 'fp8_mfma' (e4m3 weights AND per-token "
+                             "e4m3 activations on the fp8 MFMA for prefill) or 'int4' (4-bit weights with group scales in the captured decode step)")
+        if lm_weights == "int4":
+            from .quant import int4_refusal
+
+            why = int4_refusal(config)
+            if why is None and parts is not None and "opt" not in parts:
+                why = "the int4 kernels are built for the OPT language model, which this engine does not hold"
+            if why is not None:
+                raise NotImplementedError(f"lm_weights='int4': {why}")
         if not torch.cuda.is_available():
             raise RuntimeError("HipEngine needs an AMD GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.lib = abi.load_hip()
@@ -63,14 +76,17 @@ class HipEngine:
         self.beam_advance_kernel = True  # its bookkeeping of a step is eilev_beam_advance; False: torch ops
         self.beam_capture = False        # replay the fused step (both kernels) from a hipGraph; it buys nothing per token there
         self.parts = tuple(parts)
-        if lm_weights not in ("bf16", "fp8", "fp8_mfma"):
-            raise ValueError("lm_weights must be 'bf16', 'fp8' (e4m3 weights, bf16 activations) or 'fp8_mfma' (e4m3 weights AND per-token "
-                             "e4m3 activations on the fp8 MFMA for prefill)")
-        if lm_weights != "bf16" and (self.is_t5 or "opt" not in self.parts):
+        if lm_weights in ("fp8", "fp8_mfma") and (self.is_t5 or "opt" not in self.parts):
             raise NotImplementedError("fp8 weights are built for the OPT language model")
         self.lm_weights = lm_weights
         self._load(named_tensors)
-        if lm_weights != "bf16":
+        # per call on an int4 engine: dict(step="eilev_w4_decode_step" (None: one new token, no step), rows=, route=, steps=decode steps run) where the captured int4 step ran, dict(step="twin", route=)
+        # where the call ran the bf16 kernels on the twin weights (beams, context, prompt lookup, host loops)
+        self.w4_stats = None
+        self._w4 = None  # (library, per-layer table, the tensors it points to) of lm_weights="int4"
+        if lm_weights == "int4":
+            self._quantize_opt_int4()
+        elif lm_weights != "bf16":
             self._quantize_opt(act_fp8=lm_weights == "fp8_mfma")
         # LayerNorm folding of the ViT blocks (profiles/HISTORY.md §3f): the folded qkv / fc1 copies (+1.1 GB at ViT-g) are built lazily by the first
         # launch large enough to use them (>= 24576 token rows); vit_ln_fold=False keeps the LayerNorm kernels for every launch
@@ -166,14 +182,47 @@ class HipEngine:
         self._w8_keep = (keep, expand)
         abi.attach_opt_w8(self.pack, per_layer, expand.data_ptr(), nb, act_fp8=act_fp8)
 
+    def _quantize_opt_int4(self):
+        """int4 weights with group scales for the OPT linears (include/eilev_w4.h; eilev_amd/quant.py): q|k|v (one [3 D, D] matrix), out_proj,
+        fc1 and fc2 of every block are quantised and packed, and eilev_w4_expand writes the matrix the int4 kernels multiply by — the bf16
+        TWIN — into the storage the bf16 weights occupy: every bf16 route of this engine (prefill, beams, context, prompt lookup, host loops,
+        classify, debug outputs) computes with the same model as the captured int4 decode step.  The int4 copies are a quarter as much memory
+        again.  Embeddings / lm_head, LayerNorms and biases stay bf16."""
+        from .quant import pack_int4, quantize_int4
+
+        d = self.dims
+        w4 = abi.load_w4()
+        if not abi.w4_supported(d):
+            raise NotImplementedError("lm_weights='int4': the int4 kernels take OPT widths that are multiples of 256")
+        table, keep = (abi.W4Layer * d.t_layers)(), []
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        for i in range(d.t_layers):
+            p = abi.OPT_PREFIX.format(i)
+            q_w = self._keep[p + "self_attn.q_proj.weight"]
+            mats = {"qkv": torch.as_strided(q_w, (3 * d.t_hidden, d.t_hidden), (d.t_hidden, 1)),  # q | k | v are one buffer (_load packs them so)
+                    "o": self._keep[p + "self_attn.out_proj.weight"], "fc1": self._keep[p + "fc1.weight"], "fc2": self._keep[p + "fc2.weight"]}
+            for name, m in mats.items():
+                q, sc = quantize_int4(m)
+                packed = pack_int4(q)
+                keep += [packed, sc]
+                setattr(table[i], name, abi.W4Matrix(packed.data_ptr(), sc.data_ptr()))
+                abi.check(w4.eilev_w4_expand(_ptr(packed), _ptr(sc), m.shape[0], m.shape[1], _ptr(m), st), "eilev_w4_expand")
+        self._w4 = (w4, table, keep)
+
+    def _w4_twin(self, route_name):
+        """An int4 engine records that a call ran the bf16 kernels on the twin weights."""
+        if getattr(self, "lm_weights", "bf16") == "int4":
+            self.w4_stats = dict(step="twin", route=route_name)
+
     def ensure_stream_layout(self, rows: int) -> bool:
         """Decode steps of 17..32 rows stream every OPT matrix once per token through gemm_rows32_kernel; in the checkpoint layout each of its
         load instructions reads 16 segments of 64 bytes a weight row apart.  Pack second copies in the kernel's fragment order (same values,
         same arithmetic: bit-identical logits; measured 4.35 -> 4.01 ms / token at batch 32).  Returns True if the copies are attached."""
         if self._stream_keep is not None:
             return bool(self._stream_keep)
-        if (not self.decode_stream_layout or self.is_t5 or "opt" not in self.parts or self.lm_weights != "bf16" or not 16 < rows <= 32):
+        if (not self.decode_stream_layout or self.is_t5 or "opt" not in self.parts or self.lm_weights not in ("bf16", "int4") or not 16 < rows <= 32):
             return False
+        head_only = self.lm_weights == "int4"  # the int4 step streams the block linears as nibbles: only its bf16 lm_head has a stream copy
         d = self.dims
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         keep, per_layer = [], []
@@ -189,6 +238,9 @@ class HipEngine:
             return out.data_ptr()
 
         for i in range(d.t_layers):
+            if head_only:
+                per_layer.append({})
+                continue
             p = abi.OPT_PREFIX.format(i)
             q = self._keep[p + "self_attn.q_proj.weight"]
             qkv = torch.as_strided(q, (3 * d.t_hidden, d.t_hidden), (d.t_hidden, 1))  # q | k | v are one buffer (_load packs them so)
@@ -574,6 +626,8 @@ class HipEngine:
             return None
         if kv_dtype != "fp8":
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', not {kv_dtype!r}")
+        if getattr(self, "lm_weights", "bf16") == "int4":
+            raise NotImplementedError("kv_cache_dtype='fp8' together with lm_weights='int4' is not built: the int4 decode step reads a bf16 KV cache")
         if not abi.kv8_supported(self.dims):
             raise NotImplementedError("kv_dtype='fp8': the fp8 KV-cache kernels take OPT head sizes 80 and 128")
         return abi.load_kv8()
@@ -665,6 +719,7 @@ class HipEngine:
         slots [0, n) are to it n tokens already generated) and eilev_greedy_select on a second counter.  The most recent graph is kept with
         its buffers and reused by a call of the same shape on the same context.  ``trace``: a list that receives the extend's logits and every
         eager step's; it turns capture off.  Returns int64 (R, steps) new tokens."""
+        self._w4_twin("greedy_context")
         d = self.dims
         R, n, _ = new_embeds.shape
         if max_new_tokens <= 0:
@@ -865,6 +920,7 @@ class HipEngine:
         decode step when there is no draft; libeilev_hip_pld.so commits and drafts.  No hipGraph: the shapes change per step.
         Counters of the call: ``self.pld_stats``.  ``trace``: a list that receives a copy of the logits every commit read (tests)."""
         d = self.dims
+        self._w4_twin("greedy_lookup")
         B, L, _ = inputs_embeds.shape
         k, n_new = self._lookup_head(B, num_tokens, ngram, max_new_tokens)
         if n_new <= 0:
@@ -932,6 +988,7 @@ class HipEngine:
                           **plan.dev_kw)
         if self._kv8(kv_dtype) is not None:
             raise NotImplementedError("kv_cache_dtype='fp8' is built for the captured device routes only: this call takes beam search or a host loop")
+        self._w4_twin(plan.route)
         if B > plan.chunk:
             # at most 32 decode rows per call: beam search of a large batch runs sample group by sample group (groups are independent in beam
             # search); every part is planned again from the caller's arguments
@@ -1158,8 +1215,17 @@ class HipEngine:
                 one_step()
                 for b, keep in zip(buffers, snap):
                     b.copy_(keep)
-            with torch.cuda.graph(graph, stream=side):
-                one_step()
+            # no cyclic garbage collection inside the capture: a dead reference cycle that still holds a device resource (an earlier
+            # CUDAGraph, say) would be finalised by whichever allocation happens to trigger the collector, and releasing it while a
+            # capture is open aborts the process (torch.cuda.graph no longer collects before it begins)
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(graph, stream=side):
+                    one_step()
+            finally:
+                if gc_was_on:
+                    gc.enable()
         torch.cuda.current_stream(self.device).wait_stream(side)
         return graph
 
@@ -1211,7 +1277,10 @@ class HipEngine:
 
         ``kv_dtype="fp8"`` (include/eilev_kv8.h): the prompt is prefilled into a bf16 cache of capacity L, quantised into an e4m3 cache of
         capacity L + max_new (eilev_kv8_quantize), the bf16 cache dropped, and the steps run eilev_kv8_decode_step.  The dtype is part of the
-        graph's key."""
+        graph's key.
+
+        An engine of ``lm_weights="int4"`` runs eilev_w4_decode_step (include/eilev_w4.h) on the same buffers; the weight mode is part of the
+        graph's key, ``self.w4_stats`` records the step."""
         d = self.dims
         B, L, _ = inputs_embeds.shape
         cap = L + max_new_tokens
@@ -1219,8 +1288,10 @@ class HipEngine:
         if n_dec > 0:
             self.ensure_stream_layout(B)
         kv8 = self._kv8(kv_dtype)
+        w4 = self._w4[0] if self.lm_weights == "int4" else None  # (an int4 engine: the int4 step; never together with kv8, which _kv8 refuses)
         graphable = use_graph and n_dec > 1 and trace is None
-        key = tuple(key) + (B, L, cap, max_new_tokens, tuple(eos), int(pad_id), str(kv_dtype))
+        route_name = str(key[0])
+        key = tuple(key) + (str(self.lm_weights), B, L, cap, max_new_tokens, tuple(eos), int(pad_id), str(kv_dtype))
         ent = self._dec_cache if (graphable and self._dec_cache is not None and self._dec_cache["key"] == key) else None
         if ent is None:
             ent = dict(key=key, graph=None,
@@ -1232,7 +1303,8 @@ class HipEngine:
                        tokens=torch.zeros(B, dtype=torch.int64, device=self.device),
                        out=torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device),
                        logits=torch.empty((B, d.vocab), dtype=torch.float32, device=self.device),
-                       ws=self._workspace("dec", (self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1) if kv8 is None else
+                       ws=self._workspace("dec", (w4.eilev_w4_workspace_bytes(C.byref(d), B) if w4 is not None else
+                                                  self.lib.eilev_opt_workspace_bytes(C.byref(d), B, 1) if kv8 is None else
                                                   kv8.eilev_kv8_workspace_bytes(C.byref(d), B))))
             if bind is not None:  # the decode step's own selection goes to buffers that are never read
                 ent.update(argmax_out=torch.zeros((B, max_new_tokens), dtype=torch.int64, device=self.device),
@@ -1265,10 +1337,14 @@ class HipEngine:
         first(last)
 
         step_fn, step_name = (self.lib.eilev_opt_decode_step, "eilev_opt_decode_step") if kv8 is None else (kv8.eilev_kv8_decode_step, "eilev_kv8_decode_step")
+        table = ()
+        if w4 is not None:  # the same arguments with the per-layer table of int4 matrices after the weights
+            step_fn, step_name, table = w4.eilev_w4_decode_step, "eilev_w4_decode_step", (self._w4[1],)
+            self.w4_stats = dict(step=step_name if n_dec > 0 else None, rows=B, route=route_name, steps=0)  # (one new token: the prefill alone)
 
         def one_step():
             abi.check(step_fn(
-                C.byref(d), C.byref(self.pack.opt), _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), B, L, _ptr(kv), cap,
+                C.byref(d), C.byref(self.pack.opt), *table, _ptr(tokens), _ptr(state), _ptr(am), _ptr(n_valid), B, L, _ptr(kv), cap,
                 _ptr(logits), _ptr(step_fin), step_eos, pad_id, _ptr(step_out), max_new_tokens, _ptr(ws), ws.numel(),
                 self._stream()), step_name)
             step(logits)
@@ -1278,6 +1354,8 @@ class HipEngine:
             graph = ent["graph"] = self._capture_step(one_step, (state, finished, tokens, out), warm=not self._decode_warm)
             self._decode_warm = True
         done_steps = self._run_steps(n_dec, one_step, graph, state, eos, poll_every, trace, logits)
+        if w4 is not None:
+            self.w4_stats["steps"] = int(done_steps)
         return self._trim_at_eos(out, 1 + done_steps, eos)
 
     def _sampling_selection(self, rows, vocab, max_new, prefix_id, eos, pad_id, generator=None, uniforms=None, no_repeat_ngram_size=0, **warp):

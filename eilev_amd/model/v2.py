@@ -286,7 +286,8 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
     def engine(self):
         """bf16 device copy of the weights + the HIP library; rebuilt when a parameter changed (optimizer step,
         load_state_dict, .to())."""
-        lm_weights = getattr(self, "hip_lm_weights", "bf16")  # "fp8": e4m3 weight-only OPT linears (set the attribute before use)
+        # "fp8": e4m3 weight-only OPT linears; "int4": 4-bit OPT linears with group scales in the captured decode step (set the attribute before use)
+        lm_weights = getattr(self, "hip_lm_weights", "bf16")
         ln_fold = bool(getattr(self, "hip_vit_ln_fold", True))  # False: large ViT launches keep their LayerNorm kernels (DESIGN 3f)
         key = (_params_key(self), lm_weights, ln_fold)
         if self._hip is None or self._hip[0] != key:
@@ -342,6 +343,9 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         # the differentiable route is chosen by what the CALL needs (labels, autograd on, a train_v2-style trainable set), see
         # _wants_graph: `model.eval()` + `loss.backward()` (fine-tuning with dropout off) gets a loss with a graph too; the module
         # mode decides whether dropout is applied, as in the reference
+        if getattr(self, "hip_lm_weights", "bf16") == "int4" and (labels is not None or (self.training and torch.is_grad_enabled())):
+            raise NotImplementedError("hip_lm_weights='int4' is an inference mode (int4 weight-only linears in the captured decode step): training "
+                                      "and labels= are not built for it")
         if labels is not None and torch.is_grad_enabled() and self._wants_graph():
             if decoder_input_ids is not None or (decoder_attention_mask is not None and not bool((decoder_attention_mask != 0).all())):
                 # (the reference's collators emit neither: ref:eilev/data/utils.py:148-200; hf derives decoder_input_ids from labels)
@@ -682,6 +686,15 @@ class VideoBlipForConditionalGeneration(PreTrainedModel):
         # the route, before any encode: from the engine that exists (its switches), else from the configuration (a new engine has them on)
         caps = route.Caps.of_config(self.config, self._hip[1] if self._hip is not None else None)
         plan = route.plan_decode(caps, r.num_beams, r.sampler, r.rules, r.eos_arg, r.min_new, r.max_new, False, r.kv_dtype)
+        if getattr(self, "hip_lm_weights", "bf16") == "int4":  # refused from the configuration and the arguments, before any encode
+            from ..quant import int4_refusal
+
+            why = int4_refusal(self.config)
+            if why is not None:
+                raise NotImplementedError(f"hip_lm_weights='int4': {why}")
+            if r.kv_dtype == "fp8":
+                raise NotImplementedError("generate(kv_cache_dtype='fp8') with hip_lm_weights='int4' is not built on the HIP path: the int4 decode "
+                                          "step reads a bf16 KV cache")
         if r.kv_dtype == "fp8":  # served by the three captured routes of the OPT decode step
             said = {"user processor": "logits_processor", "stopping criterion": "stopping criteria / max_time", "more than 8 EOS ids": "more than 8 EOS ids",
                     "vocabulary not taken": "a vocabulary the device selection does not take"}
